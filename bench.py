@@ -16,6 +16,16 @@ One "step" = one engine scheduler step (one packed forward: decode batch +
 prefill chunks). Warmup steps fill the continuous batch; then exactly K
 steps are timed between barriers + torch.cuda.synchronize on both sides.
 rank0 prints ONE JSON line; value = WHOLE-JOB output tokens/s.
+
+A plain run does only what that line needs: engine setup, warmup, the K
+timed steps. --dump-outputs DIR additionally writes what the LAST timed
+step returned to its caller (per-request sampled token, its logprob and
+the generated tokens so far, rows ordered by virtual-user id) as
+DIR/<name>.npy (float64), so two builds can be compared output for output:
+every input (weights, prompts, sampling seeds) is seeded, identical
+arguments give identical inputs. --full is where secondary measurements
+belong (anything that needs runs beyond the timed steps); today the
+headline is all this file measures, so it adds nothing.
 """
 from __future__ import annotations
 
@@ -89,7 +99,50 @@ def get_args():
         "= fp8 for the Llama configs (the reference headline model is "
         "Llama-3.1-8B-Instruct-FP8, i.e. fp8 IS the named precision).",
     )
+    p.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="after the timed steps, write the last timed step's outputs "
+        "to DIR/<name>.npy (float64)",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run the secondary measurements that need runs of their "
+        "own (none at present: the headline is the only measurement)",
+    )
     return p.parse_args()
+
+
+def dump_outputs(dirname, outputs, rid_to_vu, max_tokens, rank):
+    """Write one engine step's RequestOutputs as DIR/<name>.npy, one row per
+    request, ordered by virtual-user id (-1 / NaN = absent)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    outs = sorted(outputs, key=lambda o: rid_to_vu[o.request_id].uid)
+    n = len(outs)
+    vu_ids = np.zeros(n, dtype=np.float64)
+    new_tok = np.full(n, -1.0, dtype=np.float64)
+    logprob = np.full(n, np.nan, dtype=np.float64)
+    generated = np.full((n, max_tokens), -1.0, dtype=np.float64)
+    for i, o in enumerate(outs):
+        vu_ids[i] = rid_to_vu[o.request_id].uid
+        if o.new_token_ids:
+            new_tok[i] = o.new_token_ids[-1]
+        if o.logprob is not None:
+            logprob[i] = o.logprob
+        g = o.output_token_ids[:max_tokens]
+        generated[i, : len(g)] = g
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, arr in (
+        ("vu_ids", vu_ids),
+        ("new_token_ids", new_tok),
+        ("logprobs", logprob),
+        ("output_token_ids", generated),
+    ):
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), arr)
 
 
 def _resolve_quant(args, model, use_cuda):
@@ -242,9 +295,12 @@ def main():
                 arrival[rid] = now
                 rid_to_vu[rid] = vu
 
+    last_outputs = []  # what the most recent step returned (--dump-outputs)
+
     def one_step():
+        nonlocal last_outputs
         pump()
-        now_outputs = eng.step()
+        now_outputs = last_outputs = eng.step()
         now = time.monotonic()
         toks = 0
         for o in now_outputs:
@@ -280,6 +336,9 @@ def main():
         dist.barrier()
     t1 = time.monotonic()
     elapsed = t1 - t0
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_outputs, rid_to_vu, args.max_tokens, rank)
 
     # TTFT for requests submitted during the timed region (replica leaders)
     ttfts = [

@@ -14,13 +14,13 @@ from kubeai_amd.controlplane.manager import Manager
 from kubeai_amd.controlplane.runtime import LocalProcessRuntime
 
 
-def test_local_runtime_end_to_end():
+def test_local_runtime_end_to_end(tmp_path):
     async def body():
         cfg = SystemConfig(
             autoscaling=AutoscalingConfig(
                 interval_seconds=3600, time_window_seconds=7200, state_path=None
             ),
-            leader_lock_path="/tmp/kubeai-e2e-leader.lock",
+            leader_lock_path=str(tmp_path / "kubeai-e2e-leader.lock"),
             n_gpus=0,  # CPU engines
         )
         mgr = Manager(cfg)
@@ -71,7 +71,7 @@ def test_local_runtime_end_to_end():
     asyncio.run(body())
 
 
-def test_local_runtime_speech_to_text():
+def test_local_runtime_speech_to_text(tmp_path):
     """SpeechToText model: runtime launches the engine with task=transcribe;
     the gateway proxies a multipart transcription request end to end."""
     import io
@@ -84,7 +84,7 @@ def test_local_runtime_speech_to_text():
             autoscaling=AutoscalingConfig(
                 interval_seconds=3600, time_window_seconds=7200, state_path=None
             ),
-            leader_lock_path="/tmp/kubeai-e2e-stt-leader.lock",
+            leader_lock_path=str(tmp_path / "kubeai-e2e-stt-leader.lock"),
             n_gpus=0,
         )
         mgr = Manager(cfg)
@@ -131,7 +131,7 @@ def test_local_runtime_speech_to_text():
     asyncio.run(body())
 
 
-def test_local_runtime_bert_embeddings():
+def test_local_runtime_bert_embeddings(tmp_path):
     """Pure TextEmbedding model: runtime launches the engine with
     task=embed (BERT encoder); the gateway proxies /v1/embeddings."""
     async def body():
@@ -139,7 +139,7 @@ def test_local_runtime_bert_embeddings():
             autoscaling=AutoscalingConfig(
                 interval_seconds=3600, time_window_seconds=7200, state_path=None
             ),
-            leader_lock_path="/tmp/kubeai-e2e-emb-leader.lock",
+            leader_lock_path=str(tmp_path / "kubeai-e2e-emb-leader.lock"),
             n_gpus=0,
         )
         mgr = Manager(cfg)
