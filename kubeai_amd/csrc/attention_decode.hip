@@ -343,6 +343,39 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
   }
 }
 
+// Merge the flash-decoding partials of one (seq, q_head) across splits for
+// N contiguous output elements of that head. `po` points at the first of
+// them in split 0 (16 B aligned for N = 4, 8 B for N = 2), consecutive
+// splits are HD floats apart. The result comes back bf16-rounded, packed in
+// pairs. Every element's arithmetic is independent of N and of which lane
+// owns it, and both merge kernels go through this one helper, so they
+// produce the same bits.
+template <int N, int HD>
+DEV_INLINE void merge_partials(const float* __restrict__ po,
+                               const float* __restrict__ pml,  // [n_splits, 2]
+                               const int n_splits, uint32_t (&packed)[N / 2]) {
+  typedef float __attribute__((ext_vector_type(N))) vecN;
+  float m_star = -INFINITY;
+  for (int s = 0; s < n_splits; ++s) m_star = fmaxf(m_star, pml[2 * s]);
+  float l_star = 0.f, oo[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) oo[e] = 0.f;
+  for (int s = 0; s < n_splits; ++s) {
+    const float ms = pml[2 * s];
+    if (ms == -INFINITY) continue;
+    const float c = __expf(ms - m_star);
+    l_star += pml[2 * s + 1] * c;
+    const vecN pv = *reinterpret_cast<const vecN*>(po + s * HD);
+#pragma unroll
+    for (int e = 0; e < N; ++e) oo[e] += pv[e] * c;
+  }
+  const float inv_l = 1.0f / l_star;
+#pragma unroll
+  for (int e = 0; e < N; e += 2)
+    packed[e / 2] = ((uint32_t)f32_to_bf16(oo[e + 1] * inv_l) << 16) |
+                    f32_to_bf16(oo[e] * inv_l);
+}
+
 // Merge flash-decoding partials: one wave per (seq, q_head).
 template <int HD = 128>
 __global__ void decode_merge_kernel(
@@ -355,37 +388,96 @@ __global__ void decode_merge_kernel(
                      threadIdx.x / WAVE_SIZE;
   if (bh >= n_bh) return;
   const int lane = threadIdx.x % WAVE_SIZE;
-  const float* pml = part_ml + bh * n_splits * 2;
-  const float* po = part_o + bh * n_splits * HD;
-  float m_star = -INFINITY;
-  for (int s = 0; s < n_splits; ++s) m_star = fmaxf(m_star, pml[2 * s]);
-  float l_star = 0.f, oo[EPL];
-#pragma unroll
-  for (int e = 0; e < EPL; ++e) oo[e] = 0.f;
-  for (int s = 0; s < n_splits; ++s) {
-    const float ms = pml[2 * s];
-    if (ms == -INFINITY) continue;
-    const float c = __expf(ms - m_star);
-    l_star += pml[2 * s + 1] * c;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) oo[e] += po[s * HD + EPL * lane + e] * c;
-  }
-  const float inv_l = 1.0f / l_star;
+  uint32_t packed[EPL / 2];
+  merge_partials<EPL, HD>(part_o + bh * n_splits * HD + EPL * lane,
+                          part_ml + bh * n_splits * 2, n_splits, packed);
   ushort* oh = out + bh * HD;
 #pragma unroll
-  for (int e = 0; e < EPL; e += 2) {
-    uint32_t packed = ((uint32_t)f32_to_bf16(oo[e + 1] * inv_l) << 16) |
-                      f32_to_bf16(oo[e] * inv_l);
-    *reinterpret_cast<uint32_t*>(&oh[EPL * lane + e]) = packed;
+  for (int e = 0; e < EPL; e += 2)
+    *reinterpret_cast<uint32_t*>(&oh[EPL * lane + e]) = packed[e / 2];
+}
+
+// Merge + fp8 row quantization: one workgroup per sequence, covering all
+// n_q heads, so the o_proj input (e4m3 bytes + row scale) comes out of the
+// merge instead of a quant_fp8 launch that re-reads `out` from HBM.
+// A thread owns 4 contiguous elements of the [n_q*hd] row per pass
+// (HD/4 threads per head) and keeps them, bf16-rounded, in registers under
+// the compile-time pass count; the row amax is taken over the bf16-ROUNDED
+// values, so bytes and scale equal quant_fp8_kernel run on `out`.
+constexpr int kMergeVec = 4;
+constexpr int kMergeMaxThreads = 1024;
+constexpr int kMergeMaxPasses = 2;  // rows up to 1024*4*2 = 8192 elements
+constexpr int kMergeRowMax = kMergeMaxThreads * kMergeVec * kMergeMaxPasses;
+
+template <int HD, int kPasses>
+__launch_bounds__(kMergeMaxThreads) __global__ void decode_merge_fp8_kernel(
+    ushort* __restrict__ out,             // [B, n_q, hd]
+    unsigned char* __restrict__ out_fp8,  // [B, n_q*hd] e4m3
+    float* __restrict__ out_scale,        // [B]
+    const float* __restrict__ part_o,     // [B, n_q, n_splits, hd]
+    const float* __restrict__ part_ml,    // [B, n_q, n_splits, 2]
+    const int n_q, const int n_splits) {
+  __shared__ float red[16];
+  const int b = blockIdx.x;
+  const int row_len = n_q * HD;
+  const int nvec = row_len / kMergeVec;
+  ushort* orow = out + (int64_t)b * row_len;
+
+  uint32_t packed[kPasses][kMergeVec / 2];
+  float amax = 0.f;
+#pragma unroll
+  for (int it = 0; it < kPasses; ++it) {
+    const int i = threadIdx.x + it * blockDim.x;
+    if (i < nvec) {
+      const int h = (i * kMergeVec) / HD;
+      const int col = (i * kMergeVec) % HD;
+      const int64_t bh = (int64_t)b * n_q + h;
+      merge_partials<kMergeVec, HD>(part_o + bh * n_splits * HD + col,
+                                    part_ml + bh * n_splits * 2, n_splits,
+                                    packed[it]);
+      *reinterpret_cast<uint2*>(orow + i * kMergeVec) =
+          make_uint2(packed[it][0], packed[it][1]);
+#pragma unroll
+      for (int e = 0; e < kMergeVec / 2; ++e) {
+        const uint32_t pk = packed[it][e];
+        amax = fmaxf(amax, fabsf(bf16_to_f32((ushort)(pk & 0xffff))));
+        amax = fmaxf(amax, fabsf(bf16_to_f32((ushort)(pk >> 16))));
+      }
+    }
+  }
+  const float gmax = fmaxf(block_amax(amax, red), 1e-6f);
+  const float scale = gmax / 448.0f;
+  if (threadIdx.x == 0) out_scale[b] = scale;
+  const float inv_scale = 448.0f / gmax;
+  unsigned char* frow = out_fp8 + (int64_t)b * row_len;
+#pragma unroll
+  for (int it = 0; it < kPasses; ++it) {
+    const int i = threadIdx.x + it * blockDim.x;
+    if (i < nvec) {
+      uchar4 q4;
+      const uint32_t p0 = packed[it][0], p1 = packed[it][1];
+      q4.x = f32_to_fp8(bf16_to_f32((ushort)(p0 & 0xffff)) * inv_scale);
+      q4.y = f32_to_fp8(bf16_to_f32((ushort)(p0 >> 16)) * inv_scale);
+      q4.z = f32_to_fp8(bf16_to_f32((ushort)(p1 & 0xffff)) * inv_scale);
+      q4.w = f32_to_fp8(bf16_to_f32((ushort)(p1 >> 16)) * inv_scale);
+      *reinterpret_cast<uchar4*>(frow + i * kMergeVec) = q4;
+    }
   }
 }
 
 }  // namespace
 
-void paged_attention_decode(torch::Tensor out, torch::Tensor q,
-                            torch::Tensor k_cache, torch::Tensor v_cache,
-                            torch::Tensor block_tables, torch::Tensor seq_lens,
-                            double scale, int64_t window, double softcap) {
+void quant_fp8(torch::Tensor out, torch::Tensor out_scale, torch::Tensor x);
+
+namespace {
+
+// out_fp8 / out_scale non-null: also emit the e4m3 row quantization of
+// `out` viewed as [B, n_q*hd] (what quant_fp8 would produce from it).
+void decode_impl(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
+                 torch::Tensor v_cache, torch::Tensor block_tables,
+                 torch::Tensor seq_lens, double scale, int64_t window,
+                 double softcap, torch::Tensor* out_fp8,
+                 torch::Tensor* out_scale) {
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == q.size(2));
   TORCH_CHECK(out.is_contiguous());
   TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous());
@@ -487,6 +579,33 @@ void paged_attention_decode(torch::Tensor out, torch::Tensor q,
 #undef LAUNCH_CT_HD
 #undef LAUNCH_IMPL
   HIP_CHECK_KERNEL();
+  const bool want_fp8 = out_fp8 != nullptr;
+  // fp8 in the merge: needs a merge launch and a row within its bound
+  const bool fuse_fp8 =
+      want_fp8 && n_splits > 1 && (int64_t)n_q * hd <= kMergeRowMax;
+  if (fuse_fp8) {
+    const int nvec = n_q * hd / kMergeVec;
+    // whole waves; one pass where the row fits 1024 threads x 4 elements
+    const int threads = std::min(
+        kMergeMaxThreads, (nvec + WAVE_SIZE - 1) / WAVE_SIZE * WAVE_SIZE);
+    const int passes = (nvec + threads - 1) / threads;
+#define LAUNCH_MERGE_FP8(HDV, PASSES)                                       \
+  hipLaunchKernelGGL((decode_merge_fp8_kernel<HDV, PASSES>), dim3(B),       \
+                     dim3(threads), 0, stream, (ushort*)out.data_ptr(),     \
+                     (unsigned char*)out_fp8->data_ptr(),                   \
+                     out_scale->data_ptr<float>(), part_o_ptr, part_ml_ptr, \
+                     n_q, n_splits)
+    if (hd == 256) {
+      if (passes == 1) LAUNCH_MERGE_FP8(256, 1);
+      else LAUNCH_MERGE_FP8(256, 2);
+    } else {
+      if (passes == 1) LAUNCH_MERGE_FP8(128, 1);
+      else LAUNCH_MERGE_FP8(128, 2);
+    }
+#undef LAUNCH_MERGE_FP8
+    HIP_CHECK_KERNEL();
+    return;
+  }
   if (n_splits > 1) {
     const int64_t n_bh = (int64_t)B * n_q;
     const int wpb = 4;
@@ -504,4 +623,32 @@ void paged_attention_decode(torch::Tensor out, torch::Tensor q,
                          n_q, n_splits, n_bh);
     HIP_CHECK_KERNEL();
   }
+  // no merge launch to fuse into (n_splits == 1) or row beyond the fused
+  // kernel's bound: plain row quantization of `out`
+  if (want_fp8) quant_fp8(*out_fp8, *out_scale, out.view({B, -1}));
+}
+
+}  // namespace
+
+void paged_attention_decode(torch::Tensor out, torch::Tensor q,
+                            torch::Tensor k_cache, torch::Tensor v_cache,
+                            torch::Tensor block_tables, torch::Tensor seq_lens,
+                            double scale, int64_t window, double softcap) {
+  decode_impl(out, q, k_cache, v_cache, block_tables, seq_lens, scale, window,
+              softcap, nullptr, nullptr);
+}
+
+void paged_attention_decode_fp8(torch::Tensor out, torch::Tensor out_fp8,
+                                torch::Tensor out_scale, torch::Tensor q,
+                                torch::Tensor k_cache, torch::Tensor v_cache,
+                                torch::Tensor block_tables,
+                                torch::Tensor seq_lens, double scale,
+                                int64_t window, double softcap) {
+  TORCH_CHECK(out_fp8.is_contiguous() && out_scale.is_contiguous());
+  TORCH_CHECK(out_fp8.scalar_type() == torch::kFloat8_e4m3fn);
+  TORCH_CHECK(out_scale.scalar_type() == torch::kFloat32);
+  TORCH_CHECK(out_fp8.numel() == out.numel() &&
+              out_scale.numel() == out.size(0));
+  decode_impl(out, q, k_cache, v_cache, block_tables, seq_lens, scale, window,
+              softcap, &out_fp8, &out_scale);
 }

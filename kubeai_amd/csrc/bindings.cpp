@@ -7,6 +7,10 @@ void fused_add_rmsnorm(torch::Tensor x, torch::Tensor residual,
                        torch::Tensor weight, double eps);
 void rope(torch::Tensor q, torch::Tensor k, torch::Tensor positions,
           torch::Tensor cos_sin);
+void rope_and_cache(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                    torch::Tensor positions, torch::Tensor cos_sin,
+                    torch::Tensor k_cache, torch::Tensor v_cache,
+                    torch::Tensor slot_mapping);
 void reshape_and_cache_fp8(torch::Tensor k, torch::Tensor v,
                            torch::Tensor k_cache, torch::Tensor v_cache,
                            torch::Tensor slot_mapping);
@@ -16,6 +20,12 @@ void paged_attention_decode(torch::Tensor out, torch::Tensor q,
                             torch::Tensor k_cache, torch::Tensor v_cache,
                             torch::Tensor block_tables, torch::Tensor seq_lens,
                             double scale, int64_t window, double softcap);
+void paged_attention_decode_fp8(torch::Tensor out, torch::Tensor out_fp8,
+                                torch::Tensor out_scale, torch::Tensor q,
+                                torch::Tensor k_cache, torch::Tensor v_cache,
+                                torch::Tensor block_tables,
+                                torch::Tensor seq_lens, double scale,
+                                int64_t window, double softcap);
 void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
                              torch::Tensor k_cache, torch::Tensor v_cache,
                              torch::Tensor block_tables,
@@ -61,11 +71,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_add_rmsnorm", &fused_add_rmsnorm,
         "in-place residual add + RMSNorm");
   m.def("rope", &rope, "NeoX rotary embedding, in-place q/k");
+  m.def("rope_and_cache", &rope_and_cache,
+        "rotary embedding (in-place q/k) fused with the paged KV cache write");
   m.def("reshape_and_cache", &reshape_and_cache, "paged KV cache write");
   m.def("reshape_and_cache_fp8", &reshape_and_cache_fp8,
         "paged KV cache write, fp8 e5m2 cache");
   m.def("paged_attention_decode", &paged_attention_decode,
         "paged attention, one query token per seq");
+  m.def("paged_attention_decode_fp8", &paged_attention_decode_fp8,
+        "paged decode attention that also emits the e4m3 row quant of out");
   m.def("paged_attention_prefill", &paged_attention_prefill,
         "paged causal flash attention over cached KV");
   m.def("gelu_and_mul", &gelu_and_mul, "GeGLU tanh-gelu(gate)*up");

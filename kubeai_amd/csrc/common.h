@@ -110,6 +110,16 @@ DEV_INLINE unsigned char f32_to_e5m2(float x) {
   return (unsigned char)__hip_cvt_float_to_fp8(x, __HIP_SATFINITE, __HIP_E5M2);
 }
 
+// ---------------- NeoX rotary pair ----------------
+// Rotates the pair (x1, x2) = (x[i], x[i + hd/2]) by (c, s) and rounds to
+// bf16. Every rotary kernel goes through this one expression so that
+// floating-point contraction cannot differ between them.
+DEV_INLINE void rope_rotate_pair(const float x1, const float x2, const float c,
+                                 const float s, ushort& o1, ushort& o2) {
+  o1 = f32_to_bf16(x1 * c - x2 * s);
+  o2 = f32_to_bf16(x2 * c + x1 * s);
+}
+
 // ---------------- wave reductions (64-wide) ----------------
 
 DEV_INLINE float wave_reduce_sum(float v) {
@@ -138,6 +148,40 @@ DEV_INLINE float block_reduce_sum(float v, float* smem) {
   for (int w = 0; w < 16; ++w)
     if (w < n_waves) total += smem[w];
   return total;
+}
+
+// block-wide amax over non-negative per-thread partials, up to 16 waves
+// (smem >= 16 floats). Every thread returns the maximum.
+DEV_INLINE float block_amax(float v, float* smem) {
+  const int wave = threadIdx.x / WAVE_SIZE;
+  const int lane = threadIdx.x % WAVE_SIZE;
+  const int n_waves = (blockDim.x + WAVE_SIZE - 1) / WAVE_SIZE;
+  v = wave_reduce_max(v);
+  if (lane == 0) smem[wave] = v;
+  __syncthreads();
+  float m = 0.f;
+#pragma unroll
+  for (int w = 0; w < 16; ++w)
+    if (w < n_waves) m = fmaxf(m, smem[w]);
+  return m;
+}
+
+// ---------------- fp8 e4m3 row quantization ----------------
+// Scale convention: per row, scale = max(|x|, 1e-6)/448; y = x * (448/max),
+// RNE cast with saturation. Every fp8 producer goes through these helpers.
+DEV_INLINE unsigned char f32_to_fp8(float x) {
+  return (unsigned char)__hip_cvt_float_to_fp8(x, __HIP_SATFINITE, __HIP_E4M3);
+}
+
+// 8 floats * inv_scale -> 8 packed e4m3 bytes
+DEV_INLINE uint2 quant8_fp8(const float (&f)[8], const float inv_scale) {
+  uchar2 packed[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    packed[j].x = f32_to_fp8(f[2 * j] * inv_scale);
+    packed[j].y = f32_to_fp8(f[2 * j + 1] * inv_scale);
+  }
+  return *reinterpret_cast<uint2*>(packed);
 }
 
 // ---------------- hash RNG (kernel/ref-identical spec) ----------------

@@ -5,6 +5,11 @@
 // bf16 loads vectorized as ushort8 (16 B/lane); the fused variant does the
 // residual-add + norm in a single HBM round trip (reference analog:
 // vLLM's fused_add_rms_norm — re-designed here, not ported).
+//
+// The row stays in registers between the two passes: the per-thread
+// iteration count is a template parameter and the loops over it are fully
+// unrolled with an `i < nvec` guard, so vals[] is indexed by constants only
+// (a runtime-indexed array is demoted to private memory).
 #include <torch/extension.h>
 
 #include "common.h"
@@ -12,10 +17,12 @@
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kMaxVecPerThread = 8;  // supports H up to 256*8*8 = 16384
+constexpr int kMaxIters = 8;  // supports H up to 256*8*8 = 16384
 
-template <bool kFused>
-__global__ void rmsnorm_kernel(
+// Element mapping i = threadIdx.x + it*kBlock: each thread sums the same
+// squares in the same order as a strided runtime loop would.
+template <bool kFused, int kIters>
+__launch_bounds__(kBlock) __global__ void rmsnorm_kernel(
     ushort* __restrict__ out,        // [T, H] bf16 (== x for fused)
     ushort* __restrict__ x,          // [T, H] bf16
     ushort* __restrict__ residual,   // [T, H] bf16 (fused only; updated)
@@ -28,43 +35,65 @@ __global__ void rmsnorm_kernel(
   const ushort8* wv = reinterpret_cast<const ushort8*>(w);
   const int nvec = H / 8;
 
-  float vals[kMaxVecPerThread][8];
+  float vals[kIters][8];
   float ssum = 0.f;
-  int n_iter = 0;
-  for (int i = threadIdx.x; i < nvec; i += kBlock, ++n_iter) {
-    ushort8 xv = xrow[i];
-    ushort8 rin;
-    if constexpr (kFused) rin = rrow[i];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float f = bf16_to_f32(xv[j]);
-      if constexpr (kFused) f += bf16_to_f32(rin[j]);
-      vals[n_iter][j] = f;
-      ssum += f * f;
-    }
-    if constexpr (kFused) {
-      // write residual' = x + residual back
-      ushort8 rv;
+  for (int it = 0; it < kIters; ++it) {
+    const int i = threadIdx.x + it * kBlock;
+    if (i < nvec) {
+      ushort8 xv = xrow[i];
+      ushort8 rin;
+      if constexpr (kFused) rin = rrow[i];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) rv[j] = f32_to_bf16(vals[n_iter][j]);
-      rrow[i] = rv;
+      for (int j = 0; j < 8; ++j) {
+        float f = bf16_to_f32(xv[j]);
+        if constexpr (kFused) f += bf16_to_f32(rin[j]);
+        vals[it][j] = f;
+        ssum += f * f;
+      }
+      if constexpr (kFused) {
+        // write residual' = x + residual back
+        ushort8 rv;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) rv[j] = f32_to_bf16(vals[it][j]);
+        rrow[i] = rv;
+      }
     }
+  }
+  // the norm weights do not depend on the reduction: load them above it
+  ushort8 wreg[kIters];
+#pragma unroll
+  for (int it = 0; it < kIters; ++it) {
+    const int i = threadIdx.x + it * kBlock;
+    if (i < nvec) wreg[it] = wv[i];
   }
 
   __shared__ float red[16];
   float total = block_reduce_sum(ssum, red);
   const float inv_rms = rsqrtf(total / (float)H + eps);
 
-  n_iter = 0;
-  for (int i = threadIdx.x; i < nvec; i += kBlock, ++n_iter) {
-    ushort8 wvv = wv[i];
-    ushort8 ov;
 #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      ov[j] = f32_to_bf16(vals[n_iter][j] * inv_rms * bf16_to_f32(wvv[j]));
-    orow[i] = ov;
+  for (int it = 0; it < kIters; ++it) {
+    const int i = threadIdx.x + it * kBlock;
+    if (i < nvec) {
+      ushort8 ov;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        ov[j] = f32_to_bf16(vals[it][j] * inv_rms * bf16_to_f32(wreg[it][j]));
+      orow[i] = ov;
+    }
   }
 }
+
+// smallest instantiated iteration count in {1, 2, 4, 8} covering the row
+#define NORM_DISPATCH(nvec, LAUNCH)                   \
+  do {                                                \
+    const int n_it_ = ((nvec) + kBlock - 1) / kBlock; \
+    if (n_it_ <= 1) { LAUNCH(1); }                    \
+    else if (n_it_ <= 2) { LAUNCH(2); }               \
+    else if (n_it_ <= 4) { LAUNCH(4); }               \
+    else { LAUNCH(8); }                               \
+  } while (0)
 
 }  // namespace
 
@@ -74,11 +103,14 @@ void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor weight,
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
   const int H = x.size(-1);
   const int T = x.numel() / H;
-  TORCH_CHECK(H % 8 == 0 && H <= kBlock * 8 * kMaxVecPerThread);
-  hipLaunchKernelGGL((rmsnorm_kernel<false>), dim3(T), dim3(kBlock), 0,
-                     c10::hip::getCurrentHIPStream().stream(),
-                     (ushort*)out.data_ptr(), (ushort*)x.data_ptr(), nullptr,
-                     (const ushort*)weight.data_ptr(), (float)eps, H);
+  TORCH_CHECK(H % 8 == 0 && H <= kBlock * 8 * kMaxIters);
+#define LAUNCH_ROW(ITERS)                                                     \
+  hipLaunchKernelGGL((rmsnorm_kernel<false, ITERS>), dim3(T), dim3(kBlock),   \
+                     0, c10::hip::getCurrentHIPStream().stream(),             \
+                     (ushort*)out.data_ptr(), (ushort*)x.data_ptr(), nullptr, \
+                     (const ushort*)weight.data_ptr(), (float)eps, H)
+  NORM_DISPATCH(H / 8, LAUNCH_ROW);
+#undef LAUNCH_ROW
   HIP_CHECK_KERNEL();
 }
 
@@ -88,11 +120,14 @@ void fused_add_rmsnorm(torch::Tensor x, torch::Tensor residual,
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
   const int H = x.size(-1);
   const int T = x.numel() / H;
-  TORCH_CHECK(H % 8 == 0 && H <= kBlock * 8 * kMaxVecPerThread);
-  hipLaunchKernelGGL((rmsnorm_kernel<true>), dim3(T), dim3(kBlock), 0,
-                     c10::hip::getCurrentHIPStream().stream(),
-                     (ushort*)x.data_ptr(), (ushort*)x.data_ptr(),
-                     (ushort*)residual.data_ptr(),
-                     (const ushort*)weight.data_ptr(), (float)eps, H);
+  TORCH_CHECK(H % 8 == 0 && H <= kBlock * 8 * kMaxIters);
+#define LAUNCH_ROW(ITERS)                                                   \
+  hipLaunchKernelGGL((rmsnorm_kernel<true, ITERS>), dim3(T), dim3(kBlock),  \
+                     0, c10::hip::getCurrentHIPStream().stream(),           \
+                     (ushort*)x.data_ptr(), (ushort*)x.data_ptr(),          \
+                     (ushort*)residual.data_ptr(),                          \
+                     (const ushort*)weight.data_ptr(), (float)eps, H)
+  NORM_DISPATCH(H / 8, LAUNCH_ROW);
+#undef LAUNCH_ROW
   HIP_CHECK_KERNEL();
 }

@@ -39,8 +39,10 @@ __global__ void rope_kernel(
     const float s = cs[half + i];
     const float x1 = bf16_to_f32(base[i]);
     const float x2 = bf16_to_f32(base[half + i]);
-    base[i] = f32_to_bf16(x1 * c - x2 * s);
-    base[half + i] = f32_to_bf16(x2 * c + x1 * s);
+    ushort o1, o2;
+    rope_rotate_pair(x1, x2, c, s, o1, o2);
+    base[i] = o1;
+    base[half + i] = o2;
   }
 }
 

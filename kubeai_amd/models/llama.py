@@ -117,22 +117,38 @@ class Attention(nn.Module):
         v = v.unflatten(-1, (self.n_kv, self.hd))
         if self.qk_norm:
             # gemma3: per-head RMSNorm ((1+w) stored as w) before rope;
-            # fp32 math, contiguous bf16 out. v follows to contiguous —
-            # the cache-write kernel wants k/v with one shared row stride
+            # fp32 math, contiguous bf16 out. v stays a view of qkv: the
+            # fused rope + cache-write kernel takes a row stride per tensor
             q = _rms_head(q, self.q_norm, self.norm_eps)
             k = _rms_head(k, self.k_norm, self.norm_eps)
-            v = v.contiguous()
         if isinstance(cos_sin, tuple):
             # (global, local) caches — gemma3 dual rope bases
             cos_sin = cos_sin[0] if self.is_global else cos_sin[1]
-        q, k = ops.rope(q, k, fb.positions, cos_sin)
         k_cache, v_cache = kv_cache
-        ops.reshape_and_cache(k, v, k_cache, v_cache, fb.slot_mapping)
+        q, k = ops.rope_and_cache(
+            q, k, v, fb.positions, cos_sin, k_cache, v_cache, fb.slot_mapping
+        )
 
         out = torch.empty(
             (T, self.n_q, self.hd), dtype=qkv.dtype, device=qkv.device
         )
         nd = fb.n_decode
+        # pure-decode fp8 step: the decode call's merge step also emits the
+        # o_proj input (fp8 + row scales), no separate quant_fp8 launch
+        if fp8_in and fb.n_prefill == 0 and nd == T and nd > 0:
+            _, a8, ascale = ops.paged_attention_decode(
+                q,
+                k_cache,
+                v_cache,
+                fb.decode_block_tables,
+                fb.decode_seq_lens,
+                self.scale,
+                out=out,
+                window=self.window,
+                softcap=self.softcap,
+                fp8_out=True,
+            )
+            return self.o_proj.forward_quantized(a8, ascale)
         if nd > 0:
             ops.paged_attention_decode(
                 q[:nd],

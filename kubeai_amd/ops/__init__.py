@@ -71,18 +71,50 @@ def reshape_and_cache(k, v, k_cache, v_cache, slot_mapping) -> None:
     ref.reshape_and_cache(k, v, k_cache, v_cache, slot_mapping)
 
 
+def rope_and_cache(q, k, v, positions, cos_sin, k_cache, v_cache, slot_mapping):
+    """rope(q, k) followed by reshape_and_cache(k, v, ...) in one launch.
+    In-place on q and k on GPU; returns (q, k). q, k and v may each carry
+    their own row stride (views into the fused qkv output, or separately
+    contiguous tensors). Tokens with slot -1 are rotated but not cached."""
+    if q.is_cuda:
+        _require_ext()
+        _C.rope_and_cache(
+            q, k, v, positions, cos_sin, k_cache, v_cache, slot_mapping
+        )
+        return q, k
+    q, k = ref.rope(q, k, positions, cos_sin)
+    ref.reshape_and_cache(k, v, k_cache, v_cache, slot_mapping)
+    return q, k
+
+
 def paged_attention_decode(
     q, k_cache, v_cache, block_tables, seq_lens, scale: float, out=None,
-    window: int = 0, softcap: float = 0.0,
+    window: int = 0, softcap: float = 0.0, fp8_out: bool = False,
 ):
     """q may be a row-strided view (fused qkv output); out must be
     contiguous (allocated here if not supplied). window > 0 enables
     sliding-window attention (Mistral/Gemma2 style: keys in
-    (pos-window, pos])."""
+    (pos-window, pos]).
+
+    fp8_out=True returns (out, fp8, row_scale) where (fp8, row_scale) is
+    quant_fp8(out.view(B, -1)): on GPU the flash-decoding merge step emits
+    it directly (no separate quantization launch)."""
     if q.is_cuda:
         _require_ext()
         if out is None:
             out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        if fp8_out:
+            B = q.shape[0]
+            o8 = torch.empty(
+                (B, q.shape[1] * q.shape[2]), dtype=torch.float8_e4m3fn,
+                device=q.device,
+            )
+            oscale = torch.empty(B, dtype=torch.float32, device=q.device)
+            _C.paged_attention_decode_fp8(
+                out, o8, oscale, q, k_cache, v_cache, block_tables, seq_lens,
+                scale, window, softcap
+            )
+            return out, o8, oscale
         _C.paged_attention_decode(
             out, q, k_cache, v_cache, block_tables, seq_lens, scale, window,
             softcap
@@ -94,7 +126,10 @@ def paged_attention_decode(
     )
     if out is not None:
         out.copy_(res)
-        return out
+        res = out
+    if fp8_out:
+        o8, oscale = ref.quant_fp8(res.reshape(res.shape[0], -1))
+        return res, o8, oscale
     return res
 
 

@@ -158,13 +158,22 @@ class TPAttention(nn.Module):
         q = q.unflatten(-1, (self.n_q, self.hd))
         k = k.unflatten(-1, (self.n_kv, self.hd))
         v = v.unflatten(-1, (self.n_kv, self.hd))
-        q, k = ops.rope(q, k, fb.positions, cos_sin)
         k_cache, v_cache = kv_cache
-        ops.reshape_and_cache(k, v, k_cache, v_cache, fb.slot_mapping)
+        q, k = ops.rope_and_cache(
+            q, k, v, fb.positions, cos_sin, k_cache, v_cache, fb.slot_mapping
+        )
         out = torch.empty(
             (T, self.n_q, self.hd), dtype=qkv.dtype, device=qkv.device
         )
         nd = fb.n_decode
+        # pure-decode fp8 step: the merge step emits the o_proj input
+        if fp8_in and fb.n_prefill == 0 and nd == T and nd > 0:
+            _, a8, ascale = ops.paged_attention_decode(
+                q, k_cache, v_cache,
+                fb.decode_block_tables, fb.decode_seq_lens, self.scale,
+                out=out, window=getattr(self, "window", 0), fp8_out=True,
+            )
+            return self.o_proj.forward_quantized(a8, ascale)  # partial sum
         if nd > 0:
             ops.paged_attention_decode(
                 q[:nd], k_cache, v_cache,
