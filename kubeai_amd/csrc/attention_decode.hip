@@ -403,7 +403,7 @@ __global__ void decode_merge_kernel(
 // A thread owns 4 contiguous elements of the [n_q*hd] row per pass
 // (HD/4 threads per head) and keeps them, bf16-rounded, in registers under
 // the compile-time pass count; the row amax is taken over the bf16-ROUNDED
-// values, so bytes and scale equal quant_fp8_kernel run on `out`.
+// values, so bytes and scale equal quant_fp8 run on `out`.
 constexpr int kMergeVec = 4;
 constexpr int kMergeMaxThreads = 1024;
 constexpr int kMergeMaxPasses = 2;  // rows up to 1024*4*2 = 8192 elements
@@ -445,10 +445,7 @@ __launch_bounds__(kMergeMaxThreads) __global__ void decode_merge_fp8_kernel(
       }
     }
   }
-  const float gmax = fmaxf(block_amax(amax, red), 1e-6f);
-  const float scale = gmax / 448.0f;
-  if (threadIdx.x == 0) out_scale[b] = scale;
-  const float inv_scale = 448.0f / gmax;
+  const float inv_scale = row_scale_fp8(amax, red, out_scale + b);
   unsigned char* frow = out_fp8 + (int64_t)b * row_len;
 #pragma unroll
   for (int it = 0; it < kPasses; ++it) {
@@ -589,20 +586,16 @@ void decode_impl(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
     const int threads = std::min(
         kMergeMaxThreads, (nvec + WAVE_SIZE - 1) / WAVE_SIZE * WAVE_SIZE);
     const int passes = (nvec + threads - 1) / threads;
-#define LAUNCH_MERGE_FP8(HDV, PASSES)                                       \
-  hipLaunchKernelGGL((decode_merge_fp8_kernel<HDV, PASSES>), dim3(B),       \
-                     dim3(threads), 0, stream, (ushort*)out.data_ptr(),     \
-                     (unsigned char*)out_fp8->data_ptr(),                   \
-                     out_scale->data_ptr<float>(), part_o_ptr, part_ml_ptr, \
-                     n_q, n_splits)
-    if (hd == 256) {
-      if (passes == 1) LAUNCH_MERGE_FP8(256, 1);
-      else LAUNCH_MERGE_FP8(256, 2);
-    } else {
-      if (passes == 1) LAUNCH_MERGE_FP8(128, 1);
-      else LAUNCH_MERGE_FP8(128, 2);
-    }
-#undef LAUNCH_MERGE_FP8
+    auto* merge = hd == 256
+                      ? (passes == 1 ? decode_merge_fp8_kernel<256, 1>
+                                     : decode_merge_fp8_kernel<256, 2>)
+                      : (passes == 1 ? decode_merge_fp8_kernel<128, 1>
+                                     : decode_merge_fp8_kernel<128, 2>);
+    hipLaunchKernelGGL(merge, dim3(B), dim3(threads), 0, stream,
+                       (ushort*)out.data_ptr(),
+                       (unsigned char*)out_fp8->data_ptr(),
+                       out_scale->data_ptr<float>(), part_o_ptr, part_ml_ptr,
+                       n_q, n_splits);
     HIP_CHECK_KERNEL();
     return;
   }

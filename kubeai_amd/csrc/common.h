@@ -184,6 +184,20 @@ DEV_INLINE uint2 quant8_fp8(const float (&f)[8], const float inv_scale) {
   return *reinterpret_cast<uint2*>(packed);
 }
 
+// Per-thread partial amax -> row scale: block amax, clamped at 1e-6;
+// thread 0 writes *scale_out = max/448; every thread returns 448/max, the
+// factor the row is multiplied by before the e4m3 cast. The one place the
+// scale arithmetic lives (`smem` as for block_amax).
+DEV_INLINE float row_scale_fp8(const float amax, float* smem,
+                               float* __restrict__ scale_out) {
+  const float gmax = fmaxf(block_amax(amax, smem), 1e-6f);
+  if (threadIdx.x == 0) *scale_out = gmax / 448.0f;
+  return 448.0f / gmax;
+}
+
+// ---------------- activations ----------------
+DEV_INLINE float silu(const float x) { return x / (1.0f + __expf(-x)); }
+
 // ---------------- hash RNG (kernel/ref-identical spec) ----------------
 //
 // Sampling uses a counter-based hash RNG so the HIP kernel and the PyTorch

@@ -328,7 +328,7 @@ class DecoderLayer(nn.Module):
             and fb.lora_ids is None
         ):
             # fp8 serving: norms/activations emit fp8 + per-row scales
-            # directly (quant_fp8.hip), so activation quantization costs
+            # directly (row_kernels.hip), so activation quantization costs
             # nothing extra; residual stays bf16
             if residual is None:
                 residual = x

@@ -7,6 +7,8 @@ reference implementations (ref.py) so the engine logic is testable anywhere.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import ref
@@ -177,8 +179,6 @@ def gelu_and_mul(x):
     return ref.gelu_and_mul(x)
 
 
-import os
-
 _USE_SKINNY = os.environ.get("KUBEAI_SKINNY_GEMM", "0") == "1"
 
 
@@ -207,11 +207,18 @@ def linear(x, weight):
     return torch.nn.functional.linear(x, weight)
 
 
+def _empty_fp8_rows(shape, device):
+    """Uninitialised (e4m3 `shape`, f32 [shape[0]] row scales) for an fp8
+    producer to fill."""
+    out = torch.empty(shape, dtype=torch.float8_e4m3fn, device=device)
+    scale = torch.empty(shape[0], dtype=torch.float32, device=device)
+    return out, scale
+
+
 def rmsnorm_fp8(x, weight, eps: float):
     """GPU-only: rmsnorm with fused per-row fp8 quantization."""
     _require_ext()
-    out = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
-    scale = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    out, scale = _empty_fp8_rows(x.shape, x.device)
     _C.rmsnorm_fp8(out, scale, x, weight, eps)
     return out, scale
 
@@ -219,8 +226,7 @@ def rmsnorm_fp8(x, weight, eps: float):
 def fused_add_rmsnorm_fp8(x, residual, weight, eps: float):
     """GPU-only, in-place residual update; returns (fp8 out, row scales)."""
     _require_ext()
-    out = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
-    scale = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    out, scale = _empty_fp8_rows(x.shape, x.device)
     _C.fused_add_rmsnorm_fp8(out, scale, x, residual, weight, eps)
     return out, scale
 
@@ -230,8 +236,7 @@ def silu_and_mul_fp8(x):
         return ref.quant_fp8(ref.silu_and_mul(x))
     _require_ext()
     T, two_i = x.shape
-    out = torch.empty((T, two_i // 2), dtype=torch.float8_e4m3fn, device=x.device)
-    scale = torch.empty(T, dtype=torch.float32, device=x.device)
+    out, scale = _empty_fp8_rows((T, two_i // 2), x.device)
     _C.silu_and_mul_fp8(out, scale, x)
     return out, scale
 
@@ -240,8 +245,7 @@ def quant_fp8(x):
     if not x.is_cuda:
         return ref.quant_fp8(x)
     _require_ext()
-    out = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
-    scale = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    out, scale = _empty_fp8_rows(x.shape, x.device)
     _C.quant_fp8(out, scale, x)
     return out, scale
 

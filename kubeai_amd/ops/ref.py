@@ -349,7 +349,7 @@ def topk_topp_sample(
 
 def quant_fp8(x: torch.Tensor):
     """Per-row dynamic OCP-e4m3 quantization (CPU reference of
-    csrc/quant_fp8.hip::quant_fp8): scale = amax/448, symmetric."""
+    csrc/row_kernels.hip::quant_fp8): scale = amax/448, symmetric."""
     xf = x.float()
     amax = xf.abs().amax(dim=-1).clamp_min(1e-6)
     scale = amax / 448.0

@@ -18,6 +18,16 @@ from torch.utils import cpp_extension  # noqa: E402
 ROOT = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(ROOT, "kubeai_amd", "csrc")
 
+# hipify writes X_hip.hip / X_hip.h next to X.hip / X.h. Delete the ones
+# whose base source is gone (renamed or removed since the last build): the
+# glob below would compile them and their symbols would collide.
+for _gen in glob.glob(os.path.join(CSRC, "*_hip.hip")) + glob.glob(
+    os.path.join(CSRC, "*_hip.h")
+):
+    _stem, _ext = os.path.splitext(_gen)
+    if not os.path.exists(_stem[: -len("_hip")] + _ext):
+        os.remove(_gen)
+
 sources = sorted(
     glob.glob(os.path.join(CSRC, "*.cpp")) + glob.glob(os.path.join(CSRC, "*.hip"))
 )
@@ -40,9 +50,7 @@ for _src in list(sources):
         _gen = _src[:-4] + "_hip.hip"
         if os.path.exists(_gen):
             os.remove(_gen)
-            sources = [s for s in sources if s != _gen]
-# drop hipify artifacts whose base source was deleted or touched
-sources = [s for s in sources if os.path.exists(s)]
+            sources.remove(_gen)
 
 setup(
     name="kubeai_amd_C",

@@ -19,7 +19,8 @@ DEV = "cuda"
 # iterations, ragged); 16384 = the 8-iteration boundary of the 256 block
 # (rmsnorm family; quant_fp8 runs it as 512 threads x 4)
 ROW_H = [264, 4104, 4096, 16384]
-# 32768: 512 threads x 8 (quant_fp8.hip row ops only)
+# 32768: 512 threads x 8, the width limit of the whole family
+# (row_kernels.hip)
 ROW_H_FP8 = ROW_H + [32768]
 ROW_T = [1, 3]
 
@@ -45,7 +46,7 @@ def _seed():
 # ---------------------------------------------------------------- row kernels
 
 
-@pytest.mark.parametrize("H", ROW_H)
+@pytest.mark.parametrize("H", ROW_H_FP8)
 @pytest.mark.parametrize("T", ROW_T)
 def test_rmsnorm_rows(T, H):
     x = torch.randn(T, H, dtype=torch.bfloat16, device=DEV)
@@ -54,7 +55,7 @@ def test_rmsnorm_rows(T, H):
     assert_close_bf16(out, ref.rmsnorm(x.float(), w.float(), 1e-5))
 
 
-@pytest.mark.parametrize("H", ROW_H)
+@pytest.mark.parametrize("H", ROW_H_FP8)
 @pytest.mark.parametrize("T", ROW_T)
 def test_fused_add_rmsnorm_rows(T, H):
     x = torch.randn(T, H, dtype=torch.bfloat16, device=DEV)
@@ -121,6 +122,40 @@ def test_silu_and_mul_fp8_rows(T, I):
     q8, scale = ops.silu_and_mul_fp8(x)
     expected = ref.silu_and_mul(x.float())
     torch.testing.assert_close(_dequant(q8, scale), expected, atol=0.07, rtol=0.07)
+
+
+# The fused and unfused norms are one kernel template, and x + 0.0f is exact
+# (randn bf16 has no exact zeros in practice, the only place a sign could
+# differ): adding a zero residual must not change a single output bit.
+@pytest.mark.parametrize("H", [264, 4104, 16384, 32768])
+@pytest.mark.parametrize("T", ROW_T)
+def test_rmsnorm_shared_load_phase(T, H):
+    x = torch.randn(T, H, dtype=torch.bfloat16, device=DEV)
+    w = torch.randn(H, dtype=torch.bfloat16, device=DEV)
+    zeros = torch.zeros_like(x)
+
+    y, res = ops.fused_add_rmsnorm(x.clone(), zeros.clone(), w, 1e-5)
+    assert torch.equal(ops.rmsnorm(x, w, 1e-5), y)
+    assert torch.equal(res, x)
+
+    q8, scale = ops.rmsnorm_fp8(x, w, 1e-5)
+    res = zeros.clone()
+    q8_f, scale_f = ops.fused_add_rmsnorm_fp8(x.clone(), res, w, 1e-5)
+    assert torch.equal(_bytes(q8_f), _bytes(q8))
+    assert torch.equal(scale_f, scale)
+    assert torch.equal(res, x)
+
+
+# 264: ragged grid (33 vectors per row); 14336: llama-3-8b; T = 300 at
+# I = 14336 is 537600 vectors, beyond the 2048 x 256 threads of the capped
+# grid, so the grid-stride loop takes a second trip
+@pytest.mark.parametrize("op", ["silu_and_mul", "gelu_and_mul"])
+@pytest.mark.parametrize("T,I", [(1, 264), (3, 264), (1, 14336), (3, 14336), (300, 14336)])
+def test_act_and_mul_rows(op, T, I):
+    x = torch.randn(T, 2 * I, dtype=torch.bfloat16, device=DEV)
+    out = getattr(ops, op)(x)
+    assert out.shape == (T, I) and out.dtype == torch.bfloat16
+    assert_close_bf16(out, getattr(ref, op)(x.float()))
 
 
 # ------------------------------------------------------------ rope_and_cache
