@@ -21,6 +21,7 @@
 
 #include <type_traits>
 
+#include "attention_plan.h"
 #include "common.h"
 
 namespace {
@@ -492,33 +493,9 @@ void decode_impl(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
   const int G = n_q / n_kv;
   TORCH_CHECK(n_q % n_kv == 0);
   if (B == 0) return;
-  // flash-decoding split: target 2048 workgroups, cap 16. Fixed-shape
-  // microbenches (scripts/sweep_decode_splits.py) mildly favor 4096, but
-  // the live bench's length mix loses ~4.5% end-to-end at 4096 (extra
-  // fp32 partial traffic + merge work inside graph replay) — same-box
-  // A/B in profiles/r01_results.md. KUBEAI_DECODE_SPLIT_TARGET overrides
-  // for tuning sweeps.
-  static const int split_target = []() {
-    const char* e = getenv("KUBEAI_DECODE_SPLIT_TARGET");
-    const int v = e ? atoi(e) : 2048;
-    return v > 0 ? v : 2048;
-  }();
-  // optional length-aware bound: >=N cache blocks per split, so short
-  // sequences don't launch mostly-empty splits (max_blocks is the widest
-  // block table this step — host-side, no device sync)
-  static const int min_blocks_per_split = []() {
-    const char* e = getenv("KUBEAI_DECODE_MIN_BLOCKS_PER_SPLIT");
-    return e ? atoi(e) : 0;
-  }();
-  int n_splits = 1;
-  const int base_wgs = B * n_kv;
-  if (base_wgs < split_target) {
-    n_splits = std::min<int>(16, (split_target + base_wgs - 1) / base_wgs);
-    if (min_blocks_per_split > 0) {
-      const int cap = std::max(1, max_blocks / min_blocks_per_split);
-      n_splits = std::min(n_splits, cap);
-    }
-  }
+  // flash-decoding split count: attn_plan::decode_n_splits (target 2048
+  // workgroups, cap 16, env overrides for tuning sweeps)
+  const int n_splits = attn_plan::decode_n_splits(B, n_kv, max_blocks);
   torch::Tensor part_o, part_ml;
   float *part_o_ptr = nullptr, *part_ml_ptr = nullptr;
   if (n_splits > 1) {

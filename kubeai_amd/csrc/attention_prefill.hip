@@ -25,6 +25,7 @@
 //   C[M=16][N=16]: lane l holds C[(l>>4)*4 + i][l&15], i=0..3 (fp32)
 #include <torch/extension.h>
 
+#include "attention_plan.h"
 #include "common.h"
 
 namespace {
@@ -292,12 +293,12 @@ __launch_bounds__(G * WAVE_SIZE) __global__ void paged_prefill_kernel(
 
 }  // namespace
 
-// attention_prefill_v2.hip; returns false when the shape is unsupported
-bool paged_attention_prefill_v2(torch::Tensor out, torch::Tensor q,
+// attention_prefill_v2.hip; nw = workgroup width from the version-2 plan
+void paged_attention_prefill_v2(torch::Tensor out, torch::Tensor q,
                                 torch::Tensor k_cache, torch::Tensor v_cache,
                                 torch::Tensor block_tables,
                                 torch::Tensor query_start_loc,
-                                torch::Tensor seq_lens, double scale);
+                                torch::Tensor seq_lens, double scale, int nw);
 
 void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
                              torch::Tensor k_cache, torch::Tensor v_cache,
@@ -328,17 +329,16 @@ void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
   // {1,2,4,8} — DEFAULT (1.5-1.8x v1 after the defer-max/VALU pass:
   // 268 TF vs 150 @Tq=8192, numerics cos=1.0 across the full isolation
   // matrix, profiles/r02_results.md). KUBEAI_PREFILL_V2=0 falls back.
-  static const bool use_v2 = []() {
-    const char* e = getenv("KUBEAI_PREFILL_V2");
-    return e == nullptr || e[0] != '0';
-  }();
-  // the v2 ladder has no sliding-window masking (interior-tile fast
-  // path assumes plain causal) — windowed models run the v1 kernel
-  // the v2 ladder covers the plain-causal hd=128 fast path only
-  if (window == 0 && softcap == 0.0 && hd == 128 && use_v2 &&
-      paged_attention_prefill_v2(out, q, k_cache, v_cache, block_tables,
-                                 query_start_loc, seq_lens, scale))
+  // Which shapes it takes, and at which workgroup width, is decided in
+  // attn_plan::prefill_plan (windows, softcap, hd 256 and small-q
+  // continuations run the v1 kernel below).
+  const attn_plan::PrefillPlan plan = attn_plan::prefill_plan(
+      q.size(0), B, n_q, n_kv, hd, max_blocks, window, softcap);
+  if (plan.version == 2) {
+    paged_attention_prefill_v2(out, q, k_cache, v_cache, block_tables,
+                               query_start_loc, seq_lens, scale, plan.waves);
     return;
+  }
   const int Tq = q.size(0);
   const int n_qtiles_max = (Tq + kQB - 1) / kQB;  // per-seq early exit
   dim3 grid(B, n_kv, n_qtiles_max);

@@ -29,6 +29,7 @@
 //   ds_read_b64_tr_b16: lane l elem j reads lds[(l&15) + j*16 + (l>>4)*64]
 #include <torch/extension.h>
 
+#include "attention_plan.h"
 #include "common.h"
 
 namespace {
@@ -449,46 +450,23 @@ void paged_prefill_v2_kernel(
 
 }  // namespace
 
-bool paged_attention_prefill_v2(torch::Tensor out, torch::Tensor q,
+// `nw` is the workgroup width attn_plan::prefill_plan chose for this shape
+// (attention_plan.h); the caller only comes here with a version-2 plan.
+void paged_attention_prefill_v2(torch::Tensor out, torch::Tensor q,
                                 torch::Tensor k_cache, torch::Tensor v_cache,
                                 torch::Tensor block_tables,
                                 torch::Tensor query_start_loc,
-                                torch::Tensor seq_lens, double scale) {
+                                torch::Tensor seq_lens, double scale,
+                                int nw) {
   const int n_q = q.size(1), hd = q.size(2);
   const int n_kv = k_cache.size(1);
   const int G = n_q / n_kv;
-  if (hd != kHD || k_cache.size(2) != kBS ||
-      (G != 1 && G != 2 && G != 4 && G != 8))
-    return false;  // caller falls back to v1
+  TORCH_CHECK(hd == kHD && k_cache.size(2) == kBS &&
+                  (G == 1 || G == 2 || G == 4 || G == 8),
+              "prefill v2: unsupported shape");
+  TORCH_CHECK((nw == 4 && G <= 4) || nw == 8, "prefill v2: bad plan");
   const int B = query_start_loc.size(0) - 1;
   const int max_blocks = block_tables.size(1);
-  // small-q chunked continuations underfill the 8-wave workgroups
-  // (few z-tiles); v1's 16-row tiles win there (profiles/r02)
-  if (q.size(0) <= 1024 && B == 1) {
-    // rough ctx estimate via block-table width (host-side, no sync)
-    const int64_t approx_L = (int64_t)max_blocks * kBS;
-    if (approx_L > 3 * q.size(0)) return false;
-  }
-  // workgroup width: 8 waves (256 q rows/WG, best arithmetic intensity)
-  // unless that would underfill the 256-CU chip — small prefills then
-  // run the 4-wave form, whose 2x workgroup count fills more CUs
-  // (measured: +11% at Tq=1024, -6% at Tq=8192 — same-box A/B).
-  // KUBEAI_V2_WAVES forces either.
-  static const int forced_waves = []() {
-    const char* e = getenv("KUBEAI_V2_WAVES");
-    return e ? atoi(e) : 0;
-  }();
-  int nw = 8;
-  if (G <= 4) {
-    if (forced_waves == 4 || forced_waves == 8) {
-      nw = forced_waves;
-    } else {
-      const int qrows8 = (8 / G) * kQB;
-      const int64_t wgs8 =
-          (int64_t)B * n_kv * ((q.size(0) + qrows8 - 1) / qrows8);
-      if (wgs8 < 256) nw = 4;
-    }
-  }
   // max q chunk rows: nw/G waves * 32
   const int qrows = (nw / G) * kQB;
   int max_qlen = 0;
@@ -499,17 +477,11 @@ bool paged_attention_prefill_v2(torch::Tensor out, torch::Tensor q,
     max_qlen = q.size(0);
   }
   const int zdim = (max_qlen + qrows - 1) / qrows;
-  static const int dbg_mode = []() {
-    const char* e = getenv("KUBEAI_V2_DBG");
-    return e ? atoi(e) : 0;
-  }();
+  const int dbg_mode = attn_plan::env_v2_dbg();
   dim3 grid(B, n_kv, zdim), block(nw * 64);
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const bool fp8_cache = k_cache.scalar_type() == torch::kFloat8_e5m2;
-  static const int occ = []() {
-    const char* e = getenv("KUBEAI_V2_OCC");
-    return e ? atoi(e) : 2;
-  }();
+  const int occ = attn_plan::env_v2_occ();
 #define LAUNCH_V2_CT_DW(GG, CT, D, W)                                     \
   hipLaunchKernelGGL((paged_prefill_v2_kernel<GG, CT, D, W, 8>), grid,    \
                      block,                                               \
@@ -558,12 +530,11 @@ bool paged_attention_prefill_v2(torch::Tensor out, torch::Tensor q,
     case 2: LAUNCH_V2(2); break;
     case 4: LAUNCH_V2(4); break;
     case 8: LAUNCH_V2(8); break;
-    default: return false;
+    default: TORCH_CHECK(false, "unsupported GQA group size ", G);
   }
 #undef LAUNCH_V2
 #undef LAUNCH_V2_CT
 #undef LAUNCH_V2_NW4
 #undef LAUNCH_V2_CT_DW
   HIP_CHECK_KERNEL();
-  return true;
 }

@@ -1,6 +1,10 @@
 // Python bindings for the kubeai_amd gfx950 HIP kernels.
 #include <torch/extension.h>
 
+#include <utility>
+
+#include "attention_plan.h"
+
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor weight,
              double eps);
 void fused_add_rmsnorm(torch::Tensor x, torch::Tensor residual,
@@ -66,7 +70,33 @@ void nucleus_accept(torch::Tensor ok, torch::Tensor logits,
                     torch::Tensor temps, torch::Tensor top_ps,
                     torch::Tensor top_ks);
 
+// the launch plans the attention launchers follow (attention_plan.h)
+static std::pair<int64_t, int64_t> prefill_plan(int64_t Tq, int64_t B,
+                                                int64_t n_q, int64_t n_kv,
+                                                int64_t hd, int64_t max_blocks,
+                                                int64_t window,
+                                                double softcap) {
+  TORCH_CHECK(n_kv > 0 && n_q % n_kv == 0);
+  const attn_plan::PrefillPlan p = attn_plan::prefill_plan(
+      Tq, (int)B, (int)n_q, (int)n_kv, (int)hd, (int)max_blocks, window,
+      softcap);
+  return {p.version, p.waves};
+}
+static int64_t decode_plan(int64_t B, int64_t n_kv, int64_t max_blocks) {
+  return attn_plan::decode_n_splits((int)B, (int)n_kv, (int)max_blocks);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("prefill_plan", &prefill_plan,
+        "(version, waves per workgroup) paged_attention_prefill launches",
+        pybind11::arg("Tq"), pybind11::arg("B"), pybind11::arg("n_q"),
+        pybind11::arg("n_kv"), pybind11::arg("hd"),
+        pybind11::arg("max_blocks"), pybind11::arg("window") = 0,
+        pybind11::arg("softcap") = 0.0);
+  m.def("decode_plan", &decode_plan,
+        "flash-decoding splits paged_attention_decode launches",
+        pybind11::arg("B"), pybind11::arg("n_kv"),
+        pybind11::arg("max_blocks"));
   m.def("rmsnorm", &rmsnorm, "RMSNorm (bf16, fp32 accum)");
   m.def("fused_add_rmsnorm", &fused_add_rmsnorm,
         "in-place residual add + RMSNorm");
