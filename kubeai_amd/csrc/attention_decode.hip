@@ -47,19 +47,37 @@ constexpr int kPad = 8;
 // CAP: compile-time softcap enable — a runtime branch in the score
 // loop measured -13% on the capless hot path (194.6 vs 169.0 us at
 // B=64 L=2048), so capped models get their own instantiation.
-template <int G, typename CT = ushort, int HD = 128, bool CAP = false>
+//
+// RAW: "raw qkv" mode of a pure-decode step (rope_cache_attention_decode).
+// q is the UNROTATED projection output and k_new / v_new hold the new
+// token's raw K/V heads. The kernel rotates q on the way into q_pack, and
+// the one wave that owns cache block (L-1)/16 rotates k, stores the new K/V
+// row into the cache at slot_mapping[b] and patches the same bytes into its
+// own LDS tile, so the row never has to come back through memory. Equals
+// rope_and_cache followed by the !RAW kernel bit for bit in out and in both
+// caches; q, k_new and v_new are only read.
+template <int G, typename CT = ushort, int HD = 128, bool CAP = false,
+          bool RAW = false>
 __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
     ushort* __restrict__ out,            // [B, n_q, hd] bf16
     const ushort* __restrict__ q,        // [B, n_q, hd] bf16
-    const CT* __restrict__ k_cache,      // [nb, n_kv, bs, hd]
-    const CT* __restrict__ v_cache,
+    // [nb, n_kv, bs, hd]; written (one row per (b, kv head)) only when RAW
+    std::conditional_t<RAW, CT*, const CT*> __restrict__ k_cache,
+    std::conditional_t<RAW, CT*, const CT*> __restrict__ v_cache,
     const int32_t* __restrict__ block_tables,  // [B, max_blocks]
     const int32_t* __restrict__ seq_lens,      // [B]
     const float scale, const float softcap, const int window,
     const int n_kv, const int max_blocks,
     const int64_t q_stride, const int n_splits,
     float* __restrict__ part_o,    // [B, n_q, n_splits, hd]
-    float* __restrict__ part_ml) { // [B, n_q, n_splits, 2]
+    float* __restrict__ part_ml,   // [B, n_q, n_splits, 2]
+    // RAW only (null / 0 otherwise)
+    const ushort* __restrict__ k_new,          // [B, n_kv, hd] bf16, unrotated
+    const ushort* __restrict__ v_new,          // [B, n_kv, hd] bf16
+    const int32_t* __restrict__ positions,     // [B]
+    const float* __restrict__ cos_sin,         // [max_pos, hd]
+    const int64_t* __restrict__ slot_mapping,  // [B]
+    const int64_t k_stride, const int64_t v_stride) {
   const int b = blockIdx.x / (n_kv * n_splits);
   const int rem = blockIdx.x % (n_kv * n_splits);
   const int kh = rem / n_splits;
@@ -68,6 +86,15 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
   const int wave = threadIdx.x / WAVE_SIZE;
   const int lane = threadIdx.x % WAVE_SIZE;
   const int L = seq_lens[b];
+  // RAW: the row's position and slot are read next to seq_lens so that the
+  // three scalar loads share one round trip (read where they are used, each
+  // cost a trip of its own: the compiler waits on a scalar load at once)
+  int pos = 0;
+  int64_t slot = -1;
+  if constexpr (RAW) {
+    pos = positions[b];
+    slot = slot_mapping[b];
+  }
   const int n_blocks = (L + kBS - 1) / kBS;
   // sliding window: the query (position L-1) attends keys in
   // (L-1-window, L-1] -> global positions >= w0; whole blocks below w0
@@ -108,12 +135,76 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
 
   // q slice for this lane's part, packed bf16 pairs (16 u32 per head)
   uint32_t q_pack[G][16];
+  if constexpr (!RAW) {
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    const uint32_t* qp = reinterpret_cast<const uint32_t*>(
-        q + (int64_t)b * q_stride + (int64_t)(kh * G + g) * HD + part * 32);
+    for (int g = 0; g < G; ++g) {
+      const uint32_t* qp = reinterpret_cast<const uint32_t*>(
+          q + (int64_t)b * q_stride + (int64_t)(kh * G + g) * HD + part * 32);
 #pragma unroll
-    for (int i = 0; i < 16; ++i) q_pack[g][i] = qp[i];
+      for (int i = 0; i < 16; ++i) q_pack[g][i] = qp[i];
+    }
+  }
+
+  // RAW: the block-table entry of this wave's first tile is asked for ahead
+  // of the prologue loads, so the tile loads can go out as soon as it is
+  // back (index clamped to a valid entry when the wave has no tile)
+  const int32_t* bt = block_tables + (int64_t)b * max_blocks;
+  const int first = blk_lo + wave;
+  int64_t blk_first = 0;
+  if constexpr (RAW) blk_first = bt[first < blk_hi ? first : 0];
+
+  // ---- RAW prologue, loads only: nothing here depends on seq_lens, so
+  // these are in flight while the seq_lens -> block table -> KV tile chain
+  // resolves (the cos_sin row sits at the depth of the block-table load)
+  constexpr int HALF = HD / 2;
+  // q: the group's G*HALF rotary pairs are spread over the wave, 4 pairs
+  // per lane and pass (8 B loads), instead of every lane rotating its own
+  // 32-element slice of every head (16x redundant across the token lanes)
+  constexpr int QV = G * HALF / 4;                        // 4-pair vectors
+  constexpr int QIT = (QV + WAVE_SIZE - 1) / WAVE_SIZE;   // passes
+  ushort4_t q_lo[RAW ? QIT : 1], q_hi[RAW ? QIT : 1];
+  float4_t q_c[RAW ? QIT : 1], q_s[RAW ? QIT : 1];
+  // new K/V row: lanes [0, HD/8) take one 8-element vector of k each,
+  // lanes [HD/8, HD/4) one of v
+  constexpr int RV = HD / 8;
+  ushort8 row_own, row_par;
+  float4_t row_c[2], row_s[2];
+  const bool row_hi = (lane % RV) >= RV / 2;  // vector in the second half
+  if constexpr (RAW) {
+    const float* cs = cos_sin + (int64_t)pos * HD;
+#pragma unroll
+    for (int it = 0; it < QIT; ++it) {
+      const int idx = lane + it * WAVE_SIZE;
+      if (QV % WAVE_SIZE == 0 || idx < QV) {
+        const int g = idx / (HALF / 4);
+        const int i = (idx % (HALF / 4)) * 4;
+        const ushort* qh =
+            q + (int64_t)b * q_stride + (int64_t)(kh * G + g) * HD + i;
+        q_lo[it] = *reinterpret_cast<const ushort4_t*>(qh);
+        q_hi[it] = *reinterpret_cast<const ushort4_t*>(qh + HALF);
+        q_c[it] = *reinterpret_cast<const float4_t*>(cs + i);
+        q_s[it] = *reinterpret_cast<const float4_t*>(cs + HALF + i);
+      }
+    }
+    // every lane loads (lanes past 2 * RV repeat the first ones, v lanes
+    // load a partner and angles they do not use): no branch here, so no
+    // wait ahead of the block-table load
+    {
+      const int e0 = (lane % RV) * 8;
+      const ushort* row = ((lane / RV) % 2 == 0
+                               ? k_new + (int64_t)b * k_stride
+                               : v_new + (int64_t)b * v_stride) +
+                          (int64_t)kh * HD;
+      row_own = *reinterpret_cast<const ushort8*>(row + e0);
+      row_par = *reinterpret_cast<const ushort8*>(
+          row + (row_hi ? e0 - HALF : e0 + HALF));
+      const int i = row_hi ? e0 - HALF : e0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        row_c[h] = *reinterpret_cast<const float4_t*>(cs + i + 4 * h);
+        row_s[h] = *reinterpret_cast<const float4_t*>(cs + HALF + i + 4 * h);
+      }
+    }
   }
 
   float m[G], l[G], o[G][EPL];
@@ -125,8 +216,6 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
     for (int e = 0; e < EPL; ++e) o[g][e] = 0.f;
   }
 
-  const int32_t* bt = block_tables + (int64_t)b * max_blocks;
-
   // T14 async-stage: global loads for block n+1 issue before block n's
   // compute (their latency hides under it); the register payload lands in
   // the other LDS buffer just before it is needed. Per-wave buffers ->
@@ -136,8 +225,7 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
   constexpr int NS = (kBS * HD / 8) / WAVE_SIZE;
   StageVec stage_k[NS], stage_v[NS];  // this lane's vectors of each tile
 
-  auto issue_loads = [&](int blk_i) {
-    const int64_t blk = bt[blk_i];
+  auto issue_tile = [&](const int64_t blk) {
     const CT* base_k = k_cache + ((blk * n_kv + kh) * kBS) * HD;
     const CT* base_v = v_cache + ((blk * n_kv + kh) * kBS) * HD;
     const StageVec* src_k = reinterpret_cast<const StageVec*>(base_k);
@@ -148,6 +236,7 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
       stage_v[i] = src_v[lane + i * WAVE_SIZE];
     }
   };
+  auto issue_loads = [&](int blk_i) { issue_tile(bt[blk_i]); };
   auto write_tile = [&](int buf) {
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
@@ -161,17 +250,111 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
     }
   };
 
-  const int first = blk_lo + wave;
   int cur = 0;
   if (first < blk_hi) {
-    issue_loads(first);
-    write_tile(0);
+    if constexpr (RAW)
+      issue_tile(blk_first);
+    else
+      issue_loads(first);
   }
+
+  // the new row's cache block and the bytes this lane patches into its
+  // LDS tile; row_blk stays -1 in every wave but the owner
+  int row_blk = -1;
+  StageVec row_vec{};
+  if constexpr (RAW) {
+    // rotate q through the merge scratch of this wave (idle until the
+    // epilogue, private to the wave until the barrier there): bf16 [G][HD]
+    ushort* q_rot = reinterpret_cast<ushort*>(&merge_o[wave][0][0]);
+#pragma unroll
+    for (int it = 0; it < QIT; ++it) {
+      const int idx = lane + it * WAVE_SIZE;
+      if (QV % WAVE_SIZE == 0 || idx < QV) {
+        const int g = idx / (HALF / 4);
+        const int i = (idx % (HALF / 4)) * 4;
+        ushort4_t r_lo, r_hi;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          ushort o1, o2;
+          rope_rotate_pair(bf16_to_f32(q_lo[it][e]), bf16_to_f32(q_hi[it][e]),
+                           q_c[it][e], q_s[it][e], o1, o2);
+          r_lo[e] = o1;
+          r_hi[e] = o2;
+        }
+        *reinterpret_cast<ushort4_t*>(q_rot + g * HD + i) = r_lo;
+        *reinterpret_cast<ushort4_t*>(q_rot + g * HD + HALF + i) = r_hi;
+      }
+    }
+    // same wave wrote and reads: LDS ops of a wave complete in order
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const uint4* qp =
+          reinterpret_cast<const uint4*>(q_rot + g * HD + part * 32);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint4 t = qp[i];
+        q_pack[g][4 * i] = t.x;
+        q_pack[g][4 * i + 1] = t.y;
+        q_pack[g][4 * i + 2] = t.z;
+        q_pack[g][4 * i + 3] = t.w;
+      }
+    }
+
+    // new K/V row: exactly one wave per (b, kv head) owns cache block
+    // (L-1)/16 — the split whose block range holds it, and in that split
+    // the wave whose stride lands on it. slot < 0 (graph pad row): nothing
+    // is stored or patched, the row attends what the cache already holds.
+    const int new_blk = (L - 1) / kBS;
+    const bool owner = slot >= 0 && L > 0 && new_blk >= blk_lo &&
+                       new_blk < blk_hi && (new_blk - blk_lo) % kWaves == wave;
+    if (owner) {
+      row_blk = new_blk;
+      if (lane < 2 * RV) {
+        ushort8 row = row_own;  // v: stored as it is
+        if (lane < RV) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float x_own = bf16_to_f32(row_own[e]);
+            const float x_par = bf16_to_f32(row_par[e]);
+            ushort o1, o2;
+            rope_rotate_pair(row_hi ? x_par : x_own, row_hi ? x_own : x_par,
+                             row_c[e / 4][e % 4], row_s[e / 4][e % 4], o1, o2);
+            row[e] = row_hi ? o2 : o1;
+          }
+        }
+        if constexpr (sizeof(CT) == 2) {
+          row_vec = row;
+        } else {
+          row_vec = 0;
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            row_vec |= (uint64_t)f32_to_e5m2(bf16_to_f32((ushort)row[e]))
+                       << (8 * e);
+        }
+        CT* dst = (lane < RV ? k_cache : v_cache) +
+                  (((slot / kBS) * n_kv + kh) * kBS + slot % kBS) * HD +
+                  (lane % RV) * 8;
+        *reinterpret_cast<StageVec*>(dst) = row_vec;
+      }
+    }
+  }
+  if (first < blk_hi) write_tile(0);
 
   for (int blk_i = first; blk_i < blk_hi; blk_i += kWaves) {
     const int tile_start = blk_i * kBS;
     const int tile_len = min(kBS, L - tile_start);
     if (blk_i + kWaves < blk_hi) issue_loads(blk_i + kWaves);
+
+    if constexpr (RAW) {
+      // the tile of the new row's block was staged from memory without
+      // that row: put the bytes just stored over it (same wave as the
+      // write_tile before, program order — no barrier)
+      if (blk_i == row_blk && lane < 2 * RV) {
+        CT* dst = lane < RV ? &k_lds[wave][cur][(L - 1) % kBS][lane * 8]
+                            : &v_lds[wave][cur][(L - 1) % kBS][(lane - RV) * 8];
+        *reinterpret_cast<StageVec*>(dst) = row_vec;
+      }
+    }
 
     // TOKP tokens score per pass; kBS/TOKP passes cover the tile (one
     // pass at HD=128, two at HD=256)
@@ -344,6 +527,12 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
   }
 }
 
+// Compile-time split bounds of the merge kernels: attention_plan.h caps
+// n_splits at 16; the 8 tier keeps the common small counts at half the
+// registers.
+constexpr int kMergeSplitCapLo = 8;
+constexpr int kMergeSplitCapHi = 16;
+
 // Merge the flash-decoding partials of one (seq, q_head) across splits for
 // N contiguous output elements of that head. `po` points at the first of
 // them in split 0 (16 B aligned for N = 4, 8 B for N = 2), consecutive
@@ -351,24 +540,51 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
 // pairs. Every element's arithmetic is independent of N and of which lane
 // owns it, and both merge kernels go through this one helper, so they
 // produce the same bits.
-template <int N, int HD>
+//
+// The partials were written by workgroups all over the chip, so every load
+// here is a trip to Infinity Cache or HBM, and none of their addresses
+// depends on another. All of them are issued before any arithmetic: SCAP is
+// a compile-time bound on n_splits (kMergeSplitCaps), the load loop is fully
+// unrolled with the split index clamped to the last real split (no branch
+// between loads; the surplus copies are never used), and the arithmetic
+// loop after it is guarded by s < n_splits. A runtime loop over n_splits
+// instead costs one serialized round trip per load (two per split).
+// Arithmetic and its order are those of the runtime loop: m* as a max over
+// s, l* and o accumulated in increasing s, -inf splits skipped.
+template <int N, int HD, int SCAP>
 DEV_INLINE void merge_partials(const float* __restrict__ po,
                                const float* __restrict__ pml,  // [n_splits, 2]
                                const int n_splits, uint32_t (&packed)[N / 2]) {
   typedef float __attribute__((ext_vector_type(N))) vecN;
+  floatx2 ml[SCAP];
+  vecN pv[SCAP];
+#pragma unroll
+  for (int s = 0; s < SCAP; ++s) {
+    const int sc = min(s, n_splits - 1);
+    ml[s] = *reinterpret_cast<const floatx2*>(pml + 2 * sc);
+    pv[s] = *reinterpret_cast<const vecN*>(po + sc * HD);
+  }
+  // keep the scheduler from holding some of the loads back behind the
+  // first waits to save registers (it did, for 1 of 16 at SCAP = 8 and 12
+  // of 32 at SCAP = 16)
+  __builtin_amdgcn_sched_barrier(0);
   float m_star = -INFINITY;
-  for (int s = 0; s < n_splits; ++s) m_star = fmaxf(m_star, pml[2 * s]);
+#pragma unroll
+  for (int s = 0; s < SCAP; ++s)
+    if (s < n_splits) m_star = fmaxf(m_star, ml[s].x);
   float l_star = 0.f, oo[N];
 #pragma unroll
   for (int e = 0; e < N; ++e) oo[e] = 0.f;
-  for (int s = 0; s < n_splits; ++s) {
-    const float ms = pml[2 * s];
-    if (ms == -INFINITY) continue;
-    const float c = __expf(ms - m_star);
-    l_star += pml[2 * s + 1] * c;
-    const vecN pv = *reinterpret_cast<const vecN*>(po + s * HD);
 #pragma unroll
-    for (int e = 0; e < N; ++e) oo[e] += pv[e] * c;
+  for (int s = 0; s < SCAP; ++s) {
+    // an empty (-inf) or surplus split is skipped by keeping the old sums
+    // (selects, not a multiply by zero, and not a branch: a branch lets
+    // the compiler sink that split's loads into it, behind a wait)
+    const bool use = s < n_splits && ml[s].x != -INFINITY;
+    const float c = __expf(ml[s].x - m_star);
+    l_star = use ? l_star + ml[s].y * c : l_star;
+#pragma unroll
+    for (int e = 0; e < N; ++e) oo[e] = use ? oo[e] + pv[s][e] * c : oo[e];
   }
   const float inv_l = 1.0f / l_star;
 #pragma unroll
@@ -378,7 +594,7 @@ DEV_INLINE void merge_partials(const float* __restrict__ po,
 }
 
 // Merge flash-decoding partials: one wave per (seq, q_head).
-template <int HD = 128>
+template <int HD, int SCAP>
 __global__ void decode_merge_kernel(
     ushort* __restrict__ out,             // [B, n_q, hd]
     const float* __restrict__ part_o,     // [B, n_q, n_splits, hd]
@@ -390,8 +606,8 @@ __global__ void decode_merge_kernel(
   if (bh >= n_bh) return;
   const int lane = threadIdx.x % WAVE_SIZE;
   uint32_t packed[EPL / 2];
-  merge_partials<EPL, HD>(part_o + bh * n_splits * HD + EPL * lane,
-                          part_ml + bh * n_splits * 2, n_splits, packed);
+  merge_partials<EPL, HD, SCAP>(part_o + bh * n_splits * HD + EPL * lane,
+                                part_ml + bh * n_splits * 2, n_splits, packed);
   ushort* oh = out + bh * HD;
 #pragma unroll
   for (int e = 0; e < EPL; e += 2)
@@ -410,7 +626,7 @@ constexpr int kMergeMaxThreads = 1024;
 constexpr int kMergeMaxPasses = 2;  // rows up to 1024*4*2 = 8192 elements
 constexpr int kMergeRowMax = kMergeMaxThreads * kMergeVec * kMergeMaxPasses;
 
-template <int HD, int kPasses>
+template <int HD, int kPasses, int SCAP>
 __launch_bounds__(kMergeMaxThreads) __global__ void decode_merge_fp8_kernel(
     ushort* __restrict__ out,             // [B, n_q, hd]
     unsigned char* __restrict__ out_fp8,  // [B, n_q*hd] e4m3
@@ -433,9 +649,9 @@ __launch_bounds__(kMergeMaxThreads) __global__ void decode_merge_fp8_kernel(
       const int h = (i * kMergeVec) / HD;
       const int col = (i * kMergeVec) % HD;
       const int64_t bh = (int64_t)b * n_q + h;
-      merge_partials<kMergeVec, HD>(part_o + bh * n_splits * HD + col,
-                                    part_ml + bh * n_splits * 2, n_splits,
-                                    packed[it]);
+      merge_partials<kMergeVec, HD, SCAP>(part_o + bh * n_splits * HD + col,
+                                          part_ml + bh * n_splits * 2,
+                                          n_splits, packed[it]);
       *reinterpret_cast<uint2*>(orow + i * kMergeVec) =
           make_uint2(packed[it][0], packed[it][1]);
 #pragma unroll
@@ -469,13 +685,20 @@ void quant_fp8(torch::Tensor out, torch::Tensor out_scale, torch::Tensor x);
 
 namespace {
 
+// The extra inputs of the raw-qkv mode (rope_cache_attention_decode)
+struct RawQKV {
+  torch::Tensor k, v, positions, cos_sin, slot_mapping;
+};
+
 // out_fp8 / out_scale non-null: also emit the e4m3 row quantization of
 // `out` viewed as [B, n_q*hd] (what quant_fp8 would produce from it).
+// raw non-null: q is unrotated; rotate it, rotate raw->k and write the new
+// K/V rows into the caches inside the decode kernel.
 void decode_impl(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
                  torch::Tensor v_cache, torch::Tensor block_tables,
                  torch::Tensor seq_lens, double scale, int64_t window,
                  double softcap, torch::Tensor* out_fp8,
-                 torch::Tensor* out_scale) {
+                 torch::Tensor* out_scale, const RawQKV* raw = nullptr) {
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == q.size(2));
   TORCH_CHECK(out.is_contiguous());
   TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous());
@@ -492,6 +715,49 @@ void decode_impl(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
   TORCH_CHECK(k_cache.size(2) == kBS, "decode kernel supports block_size=16");
   const int G = n_q / n_kv;
   TORCH_CHECK(n_q % n_kv == 0);
+  TORCH_CHECK(seq_lens.numel() >= B && block_tables.size(0) >= B);
+  const ushort *k_new = nullptr, *v_new = nullptr;
+  const int32_t* positions = nullptr;
+  const float* cos_sin = nullptr;
+  const int64_t* slot_mapping = nullptr;
+  int64_t k_stride = 0, v_stride = 0;
+  if (raw != nullptr) {
+    const torch::Tensor &k = raw->k, &v = raw->v;
+    TORCH_CHECK(k.dim() == 3 && v.dim() == 3);
+    TORCH_CHECK(k.scalar_type() == torch::kBFloat16 &&
+                v.scalar_type() == torch::kBFloat16);
+    TORCH_CHECK(k.size(0) == B && k.size(1) == n_kv && k.size(2) == hd);
+    TORCH_CHECK(v.size(0) == B && v.size(1) == n_kv && v.size(2) == hd);
+    TORCH_CHECK(k.stride(2) == 1 && k.stride(1) == hd);
+    TORCH_CHECK(v.stride(2) == 1 && v.stride(1) == hd);
+    TORCH_CHECK(v_cache.sizes() == k_cache.sizes() &&
+                v_cache.scalar_type() == k_cache.scalar_type());
+    TORCH_CHECK(k_cache.size(3) == hd);
+    TORCH_CHECK(raw->positions.scalar_type() == torch::kInt32 &&
+                raw->positions.is_contiguous() && raw->positions.numel() >= B);
+    TORCH_CHECK(raw->slot_mapping.scalar_type() == torch::kInt64 &&
+                raw->slot_mapping.is_contiguous() &&
+                raw->slot_mapping.numel() >= B);
+    TORCH_CHECK(raw->cos_sin.scalar_type() == torch::kFloat32 &&
+                raw->cos_sin.dim() == 2 && raw->cos_sin.size(1) == hd &&
+                raw->cos_sin.is_contiguous());
+    // vector access: 8 B on q rows, 16 B on k / v / cos_sin / cache rows
+    auto aligned = [](const torch::Tensor& t, int64_t bytes) {
+      return reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0 &&
+             (t.dim() < 3 || t.stride(0) * t.element_size() % bytes == 0);
+    };
+    TORCH_CHECK(aligned(q, 8) && aligned(k, 16) && aligned(v, 16) &&
+                    aligned(raw->cos_sin, 16) && aligned(k_cache, 16) &&
+                    aligned(v_cache, 16),
+                "rope_cache_attention_decode: misaligned q/k/v/cos_sin/cache");
+    k_new = (const ushort*)k.data_ptr();
+    v_new = (const ushort*)v.data_ptr();
+    positions = raw->positions.data_ptr<int32_t>();
+    cos_sin = raw->cos_sin.data_ptr<float>();
+    slot_mapping = raw->slot_mapping.data_ptr<int64_t>();
+    k_stride = k.stride(0);
+    v_stride = v.stride(0);
+  }
   if (B == 0) return;
   // flash-decoding split count: attn_plan::decode_n_splits (target 2048
   // workgroups, cap 16, env overrides for tuning sweeps)
@@ -512,22 +778,30 @@ void decode_impl(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
 #define LAUNCH_CT_HD(GG, CT, HDV)                                         \
   do {                                                                    \
     if (softcap > 0.0)                                                    \
-      LAUNCH_IMPL(GG, CT, HDV, true);                                     \
+      LAUNCH_RAW(GG, CT, HDV, true);                                      \
     else                                                                  \
-      LAUNCH_IMPL(GG, CT, HDV, false);                                    \
+      LAUNCH_RAW(GG, CT, HDV, false);                                     \
   } while (0)
-#define LAUNCH_IMPL(GG, CT, HDV, CAPV)                                    \
-  hipLaunchKernelGGL((paged_decode_kernel<GG, CT, HDV, CAPV>), grid,      \
-                     block, 0,                                            \
+#define LAUNCH_RAW(GG, CT, HDV, CAPV)                                     \
+  do {                                                                    \
+    if (raw != nullptr)                                                   \
+      LAUNCH_IMPL(GG, CT, HDV, CAPV, true);                               \
+    else                                                                  \
+      LAUNCH_IMPL(GG, CT, HDV, CAPV, false);                              \
+  } while (0)
+#define LAUNCH_IMPL(GG, CT, HDV, CAPV, RAWV)                              \
+  hipLaunchKernelGGL((paged_decode_kernel<GG, CT, HDV, CAPV, RAWV>),      \
+                     grid, block, 0,                                      \
                      stream, (ushort*)out.data_ptr(),                     \
                      (const ushort*)q.data_ptr(),                         \
-                     (const CT*)k_cache.data_ptr(),                       \
-                     (const CT*)v_cache.data_ptr(),                       \
+                     (CT*)k_cache.data_ptr(),                             \
+                     (CT*)v_cache.data_ptr(),                             \
                      block_tables.data_ptr<int32_t>(),                    \
                      seq_lens.data_ptr<int32_t>(), (float)scale,          \
                      (float)softcap, (int)window, n_kv,                   \
                      max_blocks, q.stride(0), n_splits, part_o_ptr,       \
-                     part_ml_ptr)
+                     part_ml_ptr, k_new, v_new, positions, cos_sin,       \
+                     slot_mapping, k_stride, v_stride)
 #define LAUNCH(GG)                                                        \
   do {                                                                    \
     if (hd == 256) {                                                      \
@@ -551,9 +825,15 @@ void decode_impl(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
   }
 #undef LAUNCH
 #undef LAUNCH_CT_HD
+#undef LAUNCH_RAW
 #undef LAUNCH_IMPL
   HIP_CHECK_KERNEL();
   const bool want_fp8 = out_fp8 != nullptr;
+  // split-bound tier of the merge kernels
+  static_assert(kMergeSplitCapHi == 16, "decode_n_splits caps splits at 16");
+  TORCH_CHECK(n_splits <= kMergeSplitCapHi);
+  constexpr int kLo = kMergeSplitCapLo, kHi = kMergeSplitCapHi;
+  const bool lo_cap = n_splits <= kLo;
   // fp8 in the merge: needs a merge launch and a row within its bound
   const bool fuse_fp8 =
       want_fp8 && n_splits > 1 && (int64_t)n_q * hd <= kMergeRowMax;
@@ -563,11 +843,15 @@ void decode_impl(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
     const int threads = std::min(
         kMergeMaxThreads, (nvec + WAVE_SIZE - 1) / WAVE_SIZE * WAVE_SIZE);
     const int passes = (nvec + threads - 1) / threads;
-    auto* merge = hd == 256
-                      ? (passes == 1 ? decode_merge_fp8_kernel<256, 1>
-                                     : decode_merge_fp8_kernel<256, 2>)
-                      : (passes == 1 ? decode_merge_fp8_kernel<128, 1>
-                                     : decode_merge_fp8_kernel<128, 2>);
+    auto* merge =
+        lo_cap ? (hd == 256 ? (passes == 1 ? decode_merge_fp8_kernel<256, 1, kLo>
+                                           : decode_merge_fp8_kernel<256, 2, kLo>)
+                            : (passes == 1 ? decode_merge_fp8_kernel<128, 1, kLo>
+                                           : decode_merge_fp8_kernel<128, 2, kLo>))
+               : (hd == 256 ? (passes == 1 ? decode_merge_fp8_kernel<256, 1, kHi>
+                                           : decode_merge_fp8_kernel<256, 2, kHi>)
+                            : (passes == 1 ? decode_merge_fp8_kernel<128, 1, kHi>
+                                           : decode_merge_fp8_kernel<128, 2, kHi>));
     hipLaunchKernelGGL(merge, dim3(B), dim3(threads), 0, stream,
                        (ushort*)out.data_ptr(),
                        (unsigned char*)out_fp8->data_ptr(),
@@ -579,18 +863,14 @@ void decode_impl(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
   if (n_splits > 1) {
     const int64_t n_bh = (int64_t)B * n_q;
     const int wpb = 4;
-    if (hd == 256)
-      hipLaunchKernelGGL((decode_merge_kernel<256>),
-                         dim3((uint32_t)((n_bh + wpb - 1) / wpb)),
-                         dim3(wpb * WAVE_SIZE), 0, stream,
-                         (ushort*)out.data_ptr(), part_o_ptr, part_ml_ptr,
-                         n_q, n_splits, n_bh);
-    else
-      hipLaunchKernelGGL((decode_merge_kernel<128>),
-                         dim3((uint32_t)((n_bh + wpb - 1) / wpb)),
-                         dim3(wpb * WAVE_SIZE), 0, stream,
-                         (ushort*)out.data_ptr(), part_o_ptr, part_ml_ptr,
-                         n_q, n_splits, n_bh);
+    auto* merge = hd == 256 ? (lo_cap ? decode_merge_kernel<256, kLo>
+                                      : decode_merge_kernel<256, kHi>)
+                            : (lo_cap ? decode_merge_kernel<128, kLo>
+                                      : decode_merge_kernel<128, kHi>);
+    hipLaunchKernelGGL(merge, dim3((uint32_t)((n_bh + wpb - 1) / wpb)),
+                       dim3(wpb * WAVE_SIZE), 0, stream,
+                       (ushort*)out.data_ptr(), part_o_ptr, part_ml_ptr, n_q,
+                       n_splits, n_bh);
     HIP_CHECK_KERNEL();
   }
   // no merge launch to fuse into (n_splits == 1) or row beyond the fused
@@ -621,4 +901,35 @@ void paged_attention_decode_fp8(torch::Tensor out, torch::Tensor out_fp8,
               out_scale.numel() == out.size(0));
   decode_impl(out, q, k_cache, v_cache, block_tables, seq_lens, scale, window,
               softcap, &out_fp8, &out_scale);
+}
+
+// rope_and_cache followed by paged_attention_decode[_fp8] for a pure-decode
+// step, without the rope launch: the decode kernel rotates q and k itself
+// and writes the new K/V rows. Same out / fp8 bytes / row scales / cache
+// bytes as the two-op sequence. q, k and v are NOT rotated in place (the one
+// difference from rope_and_cache): they are only read.
+// Contract: row b with slot_mapping[b] >= 0 is a decode row, i.e. the slot
+// is row (L-1) % 16 of block block_tables[b][(L-1)/16] with L = seq_lens[b].
+// out_fp8 / out_scale may be undefined tensors (no fp8 output).
+void rope_cache_attention_decode(
+    torch::Tensor out, c10::optional<torch::Tensor> out_fp8,
+    c10::optional<torch::Tensor> out_scale, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor positions, torch::Tensor cos_sin,
+    torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor slot_mapping,
+    torch::Tensor block_tables, torch::Tensor seq_lens, double scale,
+    int64_t window, double softcap) {
+  const RawQKV raw{k, v, positions, cos_sin, slot_mapping};
+  if (out_fp8.has_value()) {
+    TORCH_CHECK(out_scale.has_value());
+    TORCH_CHECK(out_fp8->is_contiguous() && out_scale->is_contiguous());
+    TORCH_CHECK(out_fp8->scalar_type() == torch::kFloat8_e4m3fn);
+    TORCH_CHECK(out_scale->scalar_type() == torch::kFloat32);
+    TORCH_CHECK(out_fp8->numel() == out.numel() &&
+                out_scale->numel() == out.size(0));
+    decode_impl(out, q, k_cache, v_cache, block_tables, seq_lens, scale,
+                window, softcap, &*out_fp8, &*out_scale, &raw);
+  } else {
+    decode_impl(out, q, k_cache, v_cache, block_tables, seq_lens, scale,
+                window, softcap, nullptr, nullptr, &raw);
+  }
 }

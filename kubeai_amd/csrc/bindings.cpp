@@ -30,6 +30,13 @@ void paged_attention_decode_fp8(torch::Tensor out, torch::Tensor out_fp8,
                                 torch::Tensor block_tables,
                                 torch::Tensor seq_lens, double scale,
                                 int64_t window, double softcap);
+void rope_cache_attention_decode(
+    torch::Tensor out, c10::optional<torch::Tensor> out_fp8,
+    c10::optional<torch::Tensor> out_scale, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor positions, torch::Tensor cos_sin,
+    torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor slot_mapping,
+    torch::Tensor block_tables, torch::Tensor seq_lens, double scale,
+    int64_t window, double softcap);
 void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
                              torch::Tensor k_cache, torch::Tensor v_cache,
                              torch::Tensor block_tables,
@@ -110,6 +117,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "paged attention, one query token per seq");
   m.def("paged_attention_decode_fp8", &paged_attention_decode_fp8,
         "paged decode attention that also emits the e4m3 row quant of out");
+  m.def("rope_cache_attention_decode", &rope_cache_attention_decode,
+        "pure-decode step: rotary embedding and KV cache write inside the "
+        "decode attention kernel (q, k, v are only read)");
   m.def("paged_attention_prefill", &paged_attention_prefill,
         "paged causal flash attention over cached KV");
   m.def("gelu_and_mul", &gelu_and_mul, "GeGLU tanh-gelu(gate)*up");

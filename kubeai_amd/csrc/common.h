@@ -112,12 +112,22 @@ DEV_INLINE unsigned char f32_to_e5m2(float x) {
 
 // ---------------- NeoX rotary pair ----------------
 // Rotates the pair (x1, x2) = (x[i], x[i + hd/2]) by (c, s) and rounds to
-// bf16. Every rotary kernel goes through this one expression so that
-// floating-point contraction cannot differ between them.
+// bf16. Every rotary kernel goes through this one expression, and the
+// expression spells its own contraction: the x2 products are rounded, the
+// x1 products are fused onto them. Left to the compiler (x1 * c - x2 * s,
+// x2 * c + x1 * s under -ffp-contract=fast) which product of each sum gets
+// fused depends on the surrounding code: rope_kernel and the bf16-cache
+// rope_and_cache_kernel came out in exactly the form below, the fp8-cache
+// rope_and_cache_kernel and the decode kernel's raw-qkv prologue fused the
+// x2 * c product of o2 instead, which is one bf16 ulp apart in about one
+// element in 10^5.
 DEV_INLINE void rope_rotate_pair(const float x1, const float x2, const float c,
                                  const float s, ushort& o1, ushort& o2) {
-  o1 = f32_to_bf16(x1 * c - x2 * s);
-  o2 = f32_to_bf16(x2 * c + x1 * s);
+#pragma clang fp contract(off)
+  const float x2s = x2 * s;
+  const float x2c = x2 * c;
+  o1 = f32_to_bf16(__builtin_fmaf(x1, c, -x2s));
+  o2 = f32_to_bf16(__builtin_fmaf(x1, s, x2c));
 }
 
 // ---------------- wave reductions (64-wide) ----------------

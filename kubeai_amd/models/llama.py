@@ -125,30 +125,40 @@ class Attention(nn.Module):
             # (global, local) caches — gemma3 dual rope bases
             cos_sin = cos_sin[0] if self.is_global else cos_sin[1]
         k_cache, v_cache = kv_cache
-        q, k = ops.rope_and_cache(
-            q, k, v, fb.positions, cos_sin, k_cache, v_cache, fb.slot_mapping
-        )
-
         out = torch.empty(
             (T, self.n_q, self.hd), dtype=qkv.dtype, device=qkv.device
         )
         nd = fb.n_decode
-        # pure-decode fp8 step: the decode call's merge step also emits the
-        # o_proj input (fp8 + row scales), no separate quant_fp8 launch
-        if fp8_in and fb.n_prefill == 0 and nd == T and nd > 0:
-            _, a8, ascale = ops.paged_attention_decode(
+        if fb.n_prefill == 0 and nd == T and nd > 0 and qkv.is_cuda:
+            # pure-decode step: nothing after attention reads the rotated
+            # q/k, so the decode kernel rotates them and writes the new K/V
+            # rows itself (no rope launch). On the fp8 path its merge step
+            # also emits the o_proj input (fp8 + row scales), no separate
+            # quant_fp8 launch.
+            res = ops.rope_cache_attention_decode(
                 q,
+                k,
+                v,
+                fb.positions,
+                cos_sin,
                 k_cache,
                 v_cache,
+                fb.slot_mapping,
                 fb.decode_block_tables,
                 fb.decode_seq_lens,
                 self.scale,
                 out=out,
                 window=self.window,
                 softcap=self.softcap,
-                fp8_out=True,
+                fp8_out=fp8_in,
             )
-            return self.o_proj.forward_quantized(a8, ascale)
+            if fp8_in:
+                _, a8, ascale = res
+                return self.o_proj.forward_quantized(a8, ascale)
+            return self._o_proj_bf16(out.view(T, -1), fb, lm)
+        q, k = ops.rope_and_cache(
+            q, k, v, fb.positions, cos_sin, k_cache, v_cache, fb.slot_mapping
+        )
         if nd > 0:
             ops.paged_attention_decode(
                 q[:nd],
@@ -178,6 +188,9 @@ class Attention(nn.Module):
         if fp8_in:
             a8, ascale = ops.quant_fp8(attn_flat)
             return self.o_proj.forward_quantized(a8, ascale)
+        return self._o_proj_bf16(attn_flat, fb, lm)
+
+    def _o_proj_bf16(self, attn_flat, fb: ForwardBatch, lm) -> torch.Tensor:
         result = self.o_proj(attn_flat)
         if lm is not None and lm.active and fb.lora_ids is not None:
             lm.apply(self.layer_idx, "o", attn_flat, result, fb.lora_ids)

@@ -135,6 +135,70 @@ def paged_attention_decode(
     return res
 
 
+def decode_rope_fused() -> bool:
+    """KUBEAI_DECODE_ROPE_FUSED=0 makes rope_cache_attention_decode run the
+    two-launch sequence (rope_and_cache, then paged_attention_decode) on GPU.
+    Read at call time: the equivalence tests and A/B runs flip it."""
+    return os.environ.get("KUBEAI_DECODE_ROPE_FUSED", "1") != "0"
+
+
+def rope_cache_attention_decode(
+    q, k, v, positions, cos_sin, k_cache, v_cache, slot_mapping,
+    block_tables, seq_lens, scale: float, out=None, window: int = 0,
+    softcap: float = 0.0, fp8_out: bool = False,
+):
+    """A pure-decode step's rope_and_cache(...) followed by
+    paged_attention_decode(..., fp8_out=...) in one call: same return value,
+    and the same bytes in `out`, the fp8 output, the row scales and both
+    caches.
+
+    On GPU the decode kernel rotates q and k itself and writes the new K/V
+    rows, so there is no rope launch. Unlike rope_and_cache it does NOT write
+    the rotated q/k back: q, k and v are left untouched (nothing after
+    attention reads them on a pure-decode step).
+
+    Every row must be a decode row: slot_mapping[b] is row (L-1) % 16 of
+    block block_tables[b][(L-1) // 16] with L = seq_lens[b], or negative
+    (graph pad row: nothing is cached, the row attends what the cache
+    holds). q, k and v keep independent row strides."""
+    if q.is_cuda and decode_rope_fused():
+        _require_ext()
+        if out is None:
+            out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        o8 = oscale = None
+        if fp8_out:
+            o8, oscale = _empty_fp8_rows(
+                (q.shape[0], q.shape[1] * q.shape[2]), q.device
+            )
+        _C.rope_cache_attention_decode(
+            out, o8, oscale, q, k, v, positions, cos_sin, k_cache, v_cache,
+            slot_mapping, block_tables, seq_lens, scale, window, softcap
+        )
+        return (out, o8, oscale) if fp8_out else out
+    if not q.is_cuda:
+        # the composition of the refs (out of place, q and k untouched)
+        res = ref.rope_cache_attention_decode(
+            q, k, v, positions, cos_sin, k_cache, v_cache, slot_mapping,
+            block_tables, seq_lens, scale, window=window, softcap=softcap,
+        )
+        if out is not None:
+            out.copy_(res)
+            res = out
+        if fp8_out:
+            o8, oscale = ref.quant_fp8(res.reshape(res.shape[0], -1))
+            return res, o8, oscale
+        return res
+    # GPU with the switch off: exactly the two launches, so q and k ARE
+    # rotated in place here, as rope_and_cache does
+    qr, _ = rope_and_cache(
+        q, k, v, positions, cos_sin, k_cache, v_cache, slot_mapping
+    )
+    return paged_attention_decode(
+        qr, k_cache, v_cache, block_tables, seq_lens, scale, out=out,
+        window=window, softcap=softcap, fp8_out=fp8_out,
+    )
+
+
 def paged_attention_prefill(
     q, k_cache, v_cache, block_tables, query_start_loc, seq_lens, scale: float,
     out=None, window: int = 0, softcap: float = 0.0,

@@ -187,6 +187,31 @@ def paged_attention_decode(
     return out.to(q.dtype)
 
 
+def rope_cache_attention_decode(
+    q: torch.Tensor,  # [B, n_heads, head_dim], unrotated
+    k: torch.Tensor,  # [B, n_kv_heads, head_dim], unrotated
+    v: torch.Tensor,  # [B, n_kv_heads, head_dim]
+    positions: torch.Tensor,  # [B] int
+    cos_sin: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    slot_mapping: torch.Tensor,  # [B] int64; -1 = pad row, nothing cached
+    block_tables: torch.Tensor,
+    seq_lens: torch.Tensor,
+    scale: float,
+    window: int = 0,
+    softcap: float = 0.0,
+) -> torch.Tensor:
+    """A pure-decode step: rope, cache write, decode attention. The caches
+    are updated in place; q, k and v are left as they are."""
+    qr, kr = rope(q, k, positions, cos_sin)
+    reshape_and_cache(kr, v, k_cache, v_cache, slot_mapping)
+    return paged_attention_decode(
+        qr, k_cache, v_cache, block_tables, seq_lens, scale, window=window,
+        softcap=softcap,
+    )
+
+
 def paged_attention_prefill(
     q: torch.Tensor,  # [Tq, n_heads, head_dim] packed query tokens
     k_cache: torch.Tensor,

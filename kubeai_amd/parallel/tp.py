@@ -159,21 +159,27 @@ class TPAttention(nn.Module):
         k = k.unflatten(-1, (self.n_kv, self.hd))
         v = v.unflatten(-1, (self.n_kv, self.hd))
         k_cache, v_cache = kv_cache
-        q, k = ops.rope_and_cache(
-            q, k, v, fb.positions, cos_sin, k_cache, v_cache, fb.slot_mapping
-        )
         out = torch.empty(
             (T, self.n_q, self.hd), dtype=qkv.dtype, device=qkv.device
         )
         nd = fb.n_decode
-        # pure-decode fp8 step: the merge step emits the o_proj input
-        if fp8_in and fb.n_prefill == 0 and nd == T and nd > 0:
-            _, a8, ascale = ops.paged_attention_decode(
-                q, k_cache, v_cache,
-                fb.decode_block_tables, fb.decode_seq_lens, self.scale,
-                out=out, window=getattr(self, "window", 0), fp8_out=True,
+        if fb.n_prefill == 0 and nd == T and nd > 0 and qkv.is_cuda:
+            # pure-decode step: rope and the cache write happen inside the
+            # decode kernel; on the fp8 path the merge step emits the o_proj
+            # input (same as models/llama.py)
+            res = ops.rope_cache_attention_decode(
+                q, k, v, fb.positions, cos_sin, k_cache, v_cache,
+                fb.slot_mapping, fb.decode_block_tables, fb.decode_seq_lens,
+                self.scale, out=out, window=getattr(self, "window", 0),
+                fp8_out=fp8_in,
             )
-            return self.o_proj.forward_quantized(a8, ascale)  # partial sum
+            if fp8_in:
+                _, a8, ascale = res
+                return self.o_proj.forward_quantized(a8, ascale)  # partial sum
+            return self.o_proj(out.view(T, -1))  # partial; layer all-reduces
+        q, k = ops.rope_and_cache(
+            q, k, v, fb.positions, cos_sin, k_cache, v_cache, fb.slot_mapping
+        )
         if nd > 0:
             ops.paged_attention_decode(
                 q[:nd], k_cache, v_cache,
