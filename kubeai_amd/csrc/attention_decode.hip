@@ -21,8 +21,10 @@
 
 #include <type_traits>
 
+#include "attention_checks.h"
 #include "attention_plan.h"
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -325,6 +327,9 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
         if constexpr (sizeof(CT) == 2) {
           row_vec = row;
         } else {
+          // bf16x8_to_e5m2x8, spelled out: through the helper the compiler
+          // schedules these kernels differently
+          // (profiles/r06_launch_dispatch.md)
           row_vec = 0;
 #pragma unroll
           for (int e = 0; e < 8; ++e)
@@ -332,8 +337,7 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
                        << (8 * e);
         }
         CT* dst = (lane < RV ? k_cache : v_cache) +
-                  (((slot / kBS) * n_kv + kh) * kBS + slot % kBS) * HD +
-                  (lane % RV) * 8;
+                  cache_row_offset(slot, kBS, n_kv, kh, HD) + (lane % RV) * 8;
         *reinterpret_cast<StageVec*>(dst) = row_vec;
       }
     }
@@ -690,32 +694,31 @@ struct RawQKV {
   torch::Tensor k, v, positions, cos_sin, slot_mapping;
 };
 
-// out_fp8 / out_scale non-null: also emit the e4m3 row quantization of
-// `out` viewed as [B, n_q*hd] (what quant_fp8 would produce from it).
+// out_fp8 / out_scale set: also emit the e4m3 row quantization of `out`
+// viewed as [B, n_q*hd] (what quant_fp8 would produce from it).
 // raw non-null: q is unrotated; rotate it, rotate raw->k and write the new
 // K/V rows into the caches inside the decode kernel.
-void decode_impl(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
-                 torch::Tensor v_cache, torch::Tensor block_tables,
-                 torch::Tensor seq_lens, double scale, int64_t window,
-                 double softcap, torch::Tensor* out_fp8,
-                 torch::Tensor* out_scale, const RawQKV* raw = nullptr) {
-  TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == q.size(2));
-  TORCH_CHECK(out.is_contiguous());
-  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous());
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(k_cache.scalar_type() == torch::kBFloat16 ||
-              k_cache.scalar_type() == torch::kFloat8_e5m2);
-  TORCH_CHECK(block_tables.scalar_type() == torch::kInt32);
-  TORCH_CHECK(seq_lens.scalar_type() == torch::kInt32);
-  const int B = q.size(0), n_q = q.size(1), hd = q.size(2);
-  const int n_kv = k_cache.size(1);
-  const int max_blocks = block_tables.size(1);
-  TORCH_CHECK(hd == 128 || hd == 256,
-              "decode kernel supports head_dim 128 or 256");
-  TORCH_CHECK(k_cache.size(2) == kBS, "decode kernel supports block_size=16");
-  const int G = n_q / n_kv;
-  TORCH_CHECK(n_q % n_kv == 0);
+//
+// Instantiation set of paged_decode_kernel: the value lists of the nested
+// dispatch below, G {1,2,4,5,6,8} x hd {128,256} x cache type x CAP x RAW
+// (96); of the merge kernels: hd x split tier {8,16} (4), and x passes {1,2}
+// for the fp8 form (8).
+void decode_impl(torch::Tensor out, const c10::optional<torch::Tensor>& out_fp8,
+                 const c10::optional<torch::Tensor>& out_scale, torch::Tensor q,
+                 torch::Tensor k_cache, torch::Tensor v_cache,
+                 torch::Tensor block_tables, torch::Tensor seq_lens,
+                 double scale, int64_t window, double softcap,
+                 const RawQKV* raw = nullptr) {
+  const AttnShape s =
+      check_paged_attention(out, q, k_cache, v_cache, block_tables, seq_lens);
+  const int B = q.size(0), n_q = s.n_q, n_kv = s.n_kv, hd = s.hd;
+  const int max_blocks = s.max_blocks;
   TORCH_CHECK(seq_lens.numel() >= B && block_tables.size(0) >= B);
+  const bool want_fp8 = out_fp8.has_value();
+  if (want_fp8) {
+    TORCH_CHECK(out_scale.has_value());
+    check_fp8_out(out, *out_fp8, *out_scale);
+  }
   const ushort *k_new = nullptr, *v_new = nullptr;
   const int32_t* positions = nullptr;
   const float* cos_sin = nullptr;
@@ -774,108 +777,74 @@ void decode_impl(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
   }
   dim3 grid(B * n_kv * n_splits), block(kBlockThreads);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const bool fp8_cache = k_cache.scalar_type() == torch::kFloat8_e5m2;
-#define LAUNCH_CT_HD(GG, CT, HDV)                                         \
-  do {                                                                    \
-    if (softcap > 0.0)                                                    \
-      LAUNCH_RAW(GG, CT, HDV, true);                                      \
-    else                                                                  \
-      LAUNCH_RAW(GG, CT, HDV, false);                                     \
-  } while (0)
-#define LAUNCH_RAW(GG, CT, HDV, CAPV)                                     \
-  do {                                                                    \
-    if (raw != nullptr)                                                   \
-      LAUNCH_IMPL(GG, CT, HDV, CAPV, true);                               \
-    else                                                                  \
-      LAUNCH_IMPL(GG, CT, HDV, CAPV, false);                              \
-  } while (0)
-#define LAUNCH_IMPL(GG, CT, HDV, CAPV, RAWV)                              \
-  hipLaunchKernelGGL((paged_decode_kernel<GG, CT, HDV, CAPV, RAWV>),      \
-                     grid, block, 0,                                      \
-                     stream, (ushort*)out.data_ptr(),                     \
-                     (const ushort*)q.data_ptr(),                         \
-                     (CT*)k_cache.data_ptr(),                             \
-                     (CT*)v_cache.data_ptr(),                             \
-                     block_tables.data_ptr<int32_t>(),                    \
-                     seq_lens.data_ptr<int32_t>(), (float)scale,          \
-                     (float)softcap, (int)window, n_kv,                   \
-                     max_blocks, q.stride(0), n_splits, part_o_ptr,       \
-                     part_ml_ptr, k_new, v_new, positions, cos_sin,       \
-                     slot_mapping, k_stride, v_stride)
-#define LAUNCH(GG)                                                        \
-  do {                                                                    \
-    if (hd == 256) {                                                      \
-      /* gemma2 shapes: G <= 2 in practice, fp8 cache supported */        \
-      if (fp8_cache) LAUNCH_CT_HD(GG, unsigned char, 256);                \
-      else LAUNCH_CT_HD(GG, ushort, 256);                                 \
-    } else if (fp8_cache) {                                               \
-      LAUNCH_CT_HD(GG, unsigned char, 128);                               \
-    } else {                                                              \
-      LAUNCH_CT_HD(GG, ushort, 128);                                      \
-    }                                                                     \
-  } while (0)
-  switch (G) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    case 5: LAUNCH(5); break;
-    case 6: LAUNCH(6); break;
-    case 8: LAUNCH(8); break;
-    default: TORCH_CHECK(false, "unsupported GQA group size ", G);
-  }
-#undef LAUNCH
-#undef LAUNCH_CT_HD
-#undef LAUNCH_RAW
-#undef LAUNCH_IMPL
+  // hd 256 is the gemma2 shape (G <= 2 in practice)
+  dispatch_int<1, 2, 4, 5, 6, 8>(s.G, "GQA group size", [&](auto g) {
+    dispatch_int<128, 256>(hd, "head dim", [&](auto hdv) {
+      dispatch_bool(s.fp8_cache, [&](auto fp8) {
+        dispatch_bool(softcap > 0.0, [&](auto cap) {
+          dispatch_bool(raw != nullptr, [&](auto rawv) {
+            using CT = std::conditional_t<decltype(fp8)::value, unsigned char,
+                                          ushort>;
+            hipLaunchKernelGGL(
+                (paged_decode_kernel<decltype(g)::value, CT,
+                                     decltype(hdv)::value, decltype(cap)::value,
+                                     decltype(rawv)::value>),
+                grid, block, 0, stream, (ushort*)out.data_ptr(),
+                (const ushort*)q.data_ptr(), (CT*)k_cache.data_ptr(),
+                (CT*)v_cache.data_ptr(), block_tables.data_ptr<int32_t>(),
+                seq_lens.data_ptr<int32_t>(), (float)scale, (float)softcap,
+                (int)window, n_kv, max_blocks, q.stride(0), n_splits,
+                part_o_ptr, part_ml_ptr, k_new, v_new, positions, cos_sin,
+                slot_mapping, k_stride, v_stride);
+          });
+        });
+      });
+    });
+  });
   HIP_CHECK_KERNEL();
-  const bool want_fp8 = out_fp8 != nullptr;
-  // split-bound tier of the merge kernels
-  static_assert(kMergeSplitCapHi == 16, "decode_n_splits caps splits at 16");
-  TORCH_CHECK(n_splits <= kMergeSplitCapHi);
-  constexpr int kLo = kMergeSplitCapLo, kHi = kMergeSplitCapHi;
-  const bool lo_cap = n_splits <= kLo;
-  // fp8 in the merge: needs a merge launch and a row within its bound
-  const bool fuse_fp8 =
-      want_fp8 && n_splits > 1 && (int64_t)n_q * hd <= kMergeRowMax;
-  if (fuse_fp8) {
-    const int nvec = n_q * hd / kMergeVec;
-    // whole waves; one pass where the row fits 1024 threads x 4 elements
-    const int threads = std::min(
-        kMergeMaxThreads, (nvec + WAVE_SIZE - 1) / WAVE_SIZE * WAVE_SIZE);
-    const int passes = (nvec + threads - 1) / threads;
-    auto* merge =
-        lo_cap ? (hd == 256 ? (passes == 1 ? decode_merge_fp8_kernel<256, 1, kLo>
-                                           : decode_merge_fp8_kernel<256, 2, kLo>)
-                            : (passes == 1 ? decode_merge_fp8_kernel<128, 1, kLo>
-                                           : decode_merge_fp8_kernel<128, 2, kLo>))
-               : (hd == 256 ? (passes == 1 ? decode_merge_fp8_kernel<256, 1, kHi>
-                                           : decode_merge_fp8_kernel<256, 2, kHi>)
-                            : (passes == 1 ? decode_merge_fp8_kernel<128, 1, kHi>
-                                           : decode_merge_fp8_kernel<128, 2, kHi>));
-    hipLaunchKernelGGL(merge, dim3(B), dim3(threads), 0, stream,
-                       (ushort*)out.data_ptr(),
-                       (unsigned char*)out_fp8->data_ptr(),
-                       out_scale->data_ptr<float>(), part_o_ptr, part_ml_ptr,
-                       n_q, n_splits);
-    HIP_CHECK_KERNEL();
+  if (n_splits == 1) {
+    // no merge launch to fuse into: plain row quantization of `out`
+    if (want_fp8) quant_fp8(*out_fp8, *out_scale, out.view({B, -1}));
     return;
   }
-  if (n_splits > 1) {
-    const int64_t n_bh = (int64_t)B * n_q;
-    const int wpb = 4;
-    auto* merge = hd == 256 ? (lo_cap ? decode_merge_kernel<256, kLo>
-                                      : decode_merge_kernel<256, kHi>)
-                            : (lo_cap ? decode_merge_kernel<128, kLo>
-                                      : decode_merge_kernel<128, kHi>);
-    hipLaunchKernelGGL(merge, dim3((uint32_t)((n_bh + wpb - 1) / wpb)),
-                       dim3(wpb * WAVE_SIZE), 0, stream,
-                       (ushort*)out.data_ptr(), part_o_ptr, part_ml_ptr, n_q,
-                       n_splits, n_bh);
-    HIP_CHECK_KERNEL();
-  }
-  // no merge launch to fuse into (n_splits == 1) or row beyond the fused
-  // kernel's bound: plain row quantization of `out`
-  if (want_fp8) quant_fp8(*out_fp8, *out_scale, out.view({B, -1}));
+  static_assert(kMergeSplitCapHi == 16, "decode_n_splits caps splits at 16");
+  TORCH_CHECK(n_splits <= kMergeSplitCapHi);
+  // fp8 in the merge: needs a row within the fused kernel's bound
+  const bool fuse_fp8 = want_fp8 && (int64_t)n_q * hd <= kMergeRowMax;
+  dispatch_int<128, 256>(hd, "head dim", [&](auto hdv) {
+    // split-bound tier of the merge kernels
+    dispatch_bool(n_splits <= kMergeSplitCapLo, [&](auto lo) {
+      constexpr int HD = decltype(hdv)::value;
+      constexpr int SCAP =
+          decltype(lo)::value ? kMergeSplitCapLo : kMergeSplitCapHi;
+      if (fuse_fp8) {
+        const int nvec = n_q * hd / kMergeVec;
+        // whole waves; one pass where the row fits 1024 threads x 4 elements
+        const int threads = std::min(
+            kMergeMaxThreads, (nvec + WAVE_SIZE - 1) / WAVE_SIZE * WAVE_SIZE);
+        dispatch_int<1, 2>(
+            (nvec + threads - 1) / threads, "merge pass count", [&](auto p) {
+              hipLaunchKernelGGL(
+                  (decode_merge_fp8_kernel<HD, decltype(p)::value, SCAP>),
+                  dim3(B), dim3(threads), 0, stream, (ushort*)out.data_ptr(),
+                  (unsigned char*)out_fp8->data_ptr(),
+                  out_scale->data_ptr<float>(), part_o_ptr, part_ml_ptr, n_q,
+                  n_splits);
+            });
+      } else {
+        const int64_t n_bh = (int64_t)B * n_q;
+        const int wpb = 4;
+        hipLaunchKernelGGL((decode_merge_kernel<HD, SCAP>),
+                           dim3((uint32_t)((n_bh + wpb - 1) / wpb)),
+                           dim3(wpb * WAVE_SIZE), 0, stream,
+                           (ushort*)out.data_ptr(), part_o_ptr, part_ml_ptr,
+                           n_q, n_splits, n_bh);
+      }
+    });
+  });
+  HIP_CHECK_KERNEL();
+  // row beyond the fused kernel's bound: plain row quantization of `out`
+  if (want_fp8 && !fuse_fp8) quant_fp8(*out_fp8, *out_scale, out.view({B, -1}));
 }
 
 }  // namespace
@@ -884,8 +853,8 @@ void paged_attention_decode(torch::Tensor out, torch::Tensor q,
                             torch::Tensor k_cache, torch::Tensor v_cache,
                             torch::Tensor block_tables, torch::Tensor seq_lens,
                             double scale, int64_t window, double softcap) {
-  decode_impl(out, q, k_cache, v_cache, block_tables, seq_lens, scale, window,
-              softcap, nullptr, nullptr);
+  decode_impl(out, c10::nullopt, c10::nullopt, q, k_cache, v_cache,
+              block_tables, seq_lens, scale, window, softcap);
 }
 
 void paged_attention_decode_fp8(torch::Tensor out, torch::Tensor out_fp8,
@@ -894,13 +863,8 @@ void paged_attention_decode_fp8(torch::Tensor out, torch::Tensor out_fp8,
                                 torch::Tensor block_tables,
                                 torch::Tensor seq_lens, double scale,
                                 int64_t window, double softcap) {
-  TORCH_CHECK(out_fp8.is_contiguous() && out_scale.is_contiguous());
-  TORCH_CHECK(out_fp8.scalar_type() == torch::kFloat8_e4m3fn);
-  TORCH_CHECK(out_scale.scalar_type() == torch::kFloat32);
-  TORCH_CHECK(out_fp8.numel() == out.numel() &&
-              out_scale.numel() == out.size(0));
-  decode_impl(out, q, k_cache, v_cache, block_tables, seq_lens, scale, window,
-              softcap, &out_fp8, &out_scale);
+  decode_impl(out, out_fp8, out_scale, q, k_cache, v_cache, block_tables,
+              seq_lens, scale, window, softcap);
 }
 
 // rope_and_cache followed by paged_attention_decode[_fp8] for a pure-decode
@@ -910,7 +874,7 @@ void paged_attention_decode_fp8(torch::Tensor out, torch::Tensor out_fp8,
 // difference from rope_and_cache): they are only read.
 // Contract: row b with slot_mapping[b] >= 0 is a decode row, i.e. the slot
 // is row (L-1) % 16 of block block_tables[b][(L-1)/16] with L = seq_lens[b].
-// out_fp8 / out_scale may be undefined tensors (no fp8 output).
+// out_fp8 / out_scale may be None (no fp8 output).
 void rope_cache_attention_decode(
     torch::Tensor out, c10::optional<torch::Tensor> out_fp8,
     c10::optional<torch::Tensor> out_scale, torch::Tensor q, torch::Tensor k,
@@ -919,17 +883,6 @@ void rope_cache_attention_decode(
     torch::Tensor block_tables, torch::Tensor seq_lens, double scale,
     int64_t window, double softcap) {
   const RawQKV raw{k, v, positions, cos_sin, slot_mapping};
-  if (out_fp8.has_value()) {
-    TORCH_CHECK(out_scale.has_value());
-    TORCH_CHECK(out_fp8->is_contiguous() && out_scale->is_contiguous());
-    TORCH_CHECK(out_fp8->scalar_type() == torch::kFloat8_e4m3fn);
-    TORCH_CHECK(out_scale->scalar_type() == torch::kFloat32);
-    TORCH_CHECK(out_fp8->numel() == out.numel() &&
-                out_scale->numel() == out.size(0));
-    decode_impl(out, q, k_cache, v_cache, block_tables, seq_lens, scale,
-                window, softcap, &*out_fp8, &*out_scale, &raw);
-  } else {
-    decode_impl(out, q, k_cache, v_cache, block_tables, seq_lens, scale,
-                window, softcap, nullptr, nullptr, &raw);
-  }
+  decode_impl(out, out_fp8, out_scale, q, k_cache, v_cache, block_tables,
+              seq_lens, scale, window, softcap, &raw);
 }

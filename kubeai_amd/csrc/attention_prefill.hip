@@ -25,8 +25,12 @@
 //   C[M=16][N=16]: lane l holds C[(l>>4)*4 + i][l&15], i=0..3 (fp32)
 #include <torch/extension.h>
 
+#include <type_traits>
+
+#include "attention_checks.h"
 #include "attention_plan.h"
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -293,12 +297,14 @@ __launch_bounds__(G * WAVE_SIZE) __global__ void paged_prefill_kernel(
 
 }  // namespace
 
-// attention_prefill_v2.hip; nw = workgroup width from the version-2 plan
+// attention_prefill_v2.hip; s = the validated shape, nw = workgroup width
+// from the version-2 plan
 void paged_attention_prefill_v2(torch::Tensor out, torch::Tensor q,
                                 torch::Tensor k_cache, torch::Tensor v_cache,
                                 torch::Tensor block_tables,
                                 torch::Tensor query_start_loc,
-                                torch::Tensor seq_lens, double scale, int nw);
+                                torch::Tensor seq_lens, double scale,
+                                const AttnShape& s, int nw);
 
 void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
                              torch::Tensor k_cache, torch::Tensor v_cache,
@@ -306,24 +312,11 @@ void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
                              torch::Tensor query_start_loc,
                              torch::Tensor seq_lens, double scale,
                              int64_t window, double softcap) {
-  TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == q.size(2));
-  TORCH_CHECK(out.is_contiguous());
-  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous());
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(k_cache.scalar_type() == torch::kBFloat16 ||
-              k_cache.scalar_type() == torch::kFloat8_e5m2);
-  TORCH_CHECK(block_tables.scalar_type() == torch::kInt32);
+  const AttnShape s =
+      check_paged_attention(out, q, k_cache, v_cache, block_tables, seq_lens);
   TORCH_CHECK(query_start_loc.scalar_type() == torch::kInt32);
-  TORCH_CHECK(seq_lens.scalar_type() == torch::kInt32);
-  const int n_q = q.size(1), hd = q.size(2);
-  const int n_kv = k_cache.size(1);
+  const int n_kv = s.n_kv, max_blocks = s.max_blocks;
   const int B = seq_lens.size(0);
-  const int max_blocks = block_tables.size(1);
-  TORCH_CHECK(hd == 128 || hd == 256,
-              "prefill kernel supports head_dim 128 or 256");
-  TORCH_CHECK(k_cache.size(2) == kBS);
-  const int G = n_q / n_kv;
-  TORCH_CHECK(n_q % n_kv == 0);
   if (q.size(0) == 0) return;
   // v2: 8-wave 32x32-MFMA ladder (attention_prefill_v2.hip), G in
   // {1,2,4,8} — DEFAULT (1.5-1.8x v1 after the defer-max/VALU pass:
@@ -333,55 +326,39 @@ void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
   // attn_plan::prefill_plan (windows, softcap, hd 256 and small-q
   // continuations run the v1 kernel below).
   const attn_plan::PrefillPlan plan = attn_plan::prefill_plan(
-      q.size(0), B, n_q, n_kv, hd, max_blocks, window, softcap);
+      q.size(0), B, s.n_q, n_kv, s.hd, max_blocks, window, softcap);
   if (plan.version == 2) {
     paged_attention_prefill_v2(out, q, k_cache, v_cache, block_tables,
-                               query_start_loc, seq_lens, scale, plan.waves);
+                               query_start_loc, seq_lens, scale, s,
+                               plan.waves);
     return;
   }
   const int Tq = q.size(0);
   const int n_qtiles_max = (Tq + kQB - 1) / kQB;  // per-seq early exit
   dim3 grid(B, n_kv, n_qtiles_max);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const bool fp8_cache = k_cache.scalar_type() == torch::kFloat8_e5m2;
-#define LAUNCH_CT_HD(GG, CT, HDV)                                          \
-  do {                                                                      \
-    if (softcap > 0.0)                                                      \
-      LAUNCH_IMPL(GG, CT, HDV, true);                                       \
-    else                                                                    \
-      LAUNCH_IMPL(GG, CT, HDV, false);                                      \
-  } while (0)
-#define LAUNCH_IMPL(GG, CT, HDV, CAPV)                                      \
-  hipLaunchKernelGGL((paged_prefill_kernel<GG, CT, HDV, CAPV>), grid,       \
-                     dim3(GG * WAVE_SIZE), 0, stream,                       \
-                     (ushort*)out.data_ptr(), (const ushort*)q.data_ptr(),  \
-                     (const CT*)k_cache.data_ptr(),                         \
-                     (const CT*)v_cache.data_ptr(),                         \
-                     block_tables.data_ptr<int32_t>(),                      \
-                     query_start_loc.data_ptr<int32_t>(),                   \
-                     seq_lens.data_ptr<int32_t>(), (float)scale,            \
-                     (float)softcap, (int)window, n_kv,                     \
-                     max_blocks, q.stride(0))
-#define LAUNCH(GG)                                                         \
-  do {                                                                     \
-    if (hd == 256) {                                                       \
-      if (fp8_cache) LAUNCH_CT_HD(GG, unsigned char, 256);                  \
-      else LAUNCH_CT_HD(GG, ushort, 256);                                   \
-    } else if (fp8_cache) {                                                 \
-      LAUNCH_CT_HD(GG, unsigned char, 128);                                 \
-    } else {                                                                \
-      LAUNCH_CT_HD(GG, ushort, 128);                                        \
-    }                                                                       \
-  } while (0)
-  switch (G) {
-    case 1: LAUNCH(1); break;
-    case 2: LAUNCH(2); break;
-    case 4: LAUNCH(4); break;
-    case 8: LAUNCH(8); break;
-    default: TORCH_CHECK(false, "unsupported GQA group size ", G);
-  }
-#undef LAUNCH
-#undef LAUNCH_CT_HD
-#undef LAUNCH_IMPL
+  // instantiation set of paged_prefill_kernel: G {1,2,4,8} x hd {128,256}
+  // x cache type x CAP (32)
+  dispatch_int<1, 2, 4, 8>(s.G, "GQA group size", [&](auto g) {
+    dispatch_int<128, 256>(s.hd, "head dim", [&](auto hdv) {
+      dispatch_bool(s.fp8_cache, [&](auto fp8) {
+        dispatch_bool(softcap > 0.0, [&](auto cap) {
+          constexpr int G = decltype(g)::value;
+          using CT =
+              std::conditional_t<decltype(fp8)::value, unsigned char, ushort>;
+          hipLaunchKernelGGL(
+              (paged_prefill_kernel<G, CT, decltype(hdv)::value,
+                                    decltype(cap)::value>),
+              grid, dim3(G * WAVE_SIZE), 0, stream, (ushort*)out.data_ptr(),
+              (const ushort*)q.data_ptr(), (const CT*)k_cache.data_ptr(),
+              (const CT*)v_cache.data_ptr(), block_tables.data_ptr<int32_t>(),
+              query_start_loc.data_ptr<int32_t>(),
+              seq_lens.data_ptr<int32_t>(), (float)scale, (float)softcap,
+              (int)window, n_kv, max_blocks, q.stride(0));
+        });
+      });
+    });
+  });
   HIP_CHECK_KERNEL();
 }
+

@@ -29,8 +29,12 @@
 //   ds_read_b64_tr_b16: lane l elem j reads lds[(l&15) + j*16 + (l>>4)*64]
 #include <torch/extension.h>
 
+#include <type_traits>
+
+#include "attention_checks.h"
 #include "attention_plan.h"
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -448,93 +452,68 @@ void paged_prefill_v2_kernel(
   }
 }
 
+// The compiled forms of the kernel, as its (DBG, MINW, NW) arguments: the
+// 8-wave default, the three KUBEAI_V2_DBG bisect forms, the KUBEAI_V2_OCC=4
+// launch-bounds experiment and the 4-wave form. Instantiation set:
+// G {1,2,4,8} x cache type x these six (48).
+struct V2Form {
+  int dbg, minw, nw;
+};
+constexpr V2Form kV2Forms[] = {{0, 2, 8}, {1, 2, 8}, {2, 2, 8},
+                               {3, 2, 8}, {0, 4, 8}, {0, 2, 4}};
+
+// Index into kV2Forms for the env experiment switches and the planned
+// workgroup width; the experiment forms exist at 8 waves only (the plan
+// never pairs them with nw = 4).
+int v2_form(const int dbg_mode, const int occ, const int nw) {
+  if (dbg_mode & 3) return dbg_mode & 3;
+  if (occ == 4) return 4;
+  return nw == 4 ? 5 : 0;
+}
+
 }  // namespace
 
 // `nw` is the workgroup width attn_plan::prefill_plan chose for this shape
-// (attention_plan.h); the caller only comes here with a version-2 plan.
+// (attention_plan.h); the caller only comes here with a version-2 plan and
+// the shape `s` it validated.
 void paged_attention_prefill_v2(torch::Tensor out, torch::Tensor q,
                                 torch::Tensor k_cache, torch::Tensor v_cache,
                                 torch::Tensor block_tables,
                                 torch::Tensor query_start_loc,
                                 torch::Tensor seq_lens, double scale,
-                                int nw) {
-  const int n_q = q.size(1), hd = q.size(2);
-  const int n_kv = k_cache.size(1);
-  const int G = n_q / n_kv;
-  TORCH_CHECK(hd == kHD && k_cache.size(2) == kBS &&
+                                const AttnShape& s, int nw) {
+  const int n_kv = s.n_kv, G = s.G, max_blocks = s.max_blocks;
+  TORCH_CHECK(s.hd == kHD && k_cache.size(2) == kBS &&
                   (G == 1 || G == 2 || G == 4 || G == 8),
               "prefill v2: unsupported shape");
   TORCH_CHECK((nw == 4 && G <= 4) || nw == 8, "prefill v2: bad plan");
   const int B = query_start_loc.size(0) - 1;
-  const int max_blocks = block_tables.size(1);
-  // max q chunk rows: nw/G waves * 32
+  // q rows per workgroup: nw/G waves * 32. grid.z covers the longest
+  // sequence the batch could hold, Tq = q.size(0) rows (no host copy of
+  // query_start_loc); shorter ones exit early.
   const int qrows = (nw / G) * kQB;
-  int max_qlen = 0;
-  {
-    // host copy of query_start_loc is cheap (B+1 ints, pinned path); the
-    // engine already keeps it on device — derive grid.z from q length
-    // bound instead: Tq <= q.size(0)
-    max_qlen = q.size(0);
-  }
-  const int zdim = (max_qlen + qrows - 1) / qrows;
-  const int dbg_mode = attn_plan::env_v2_dbg();
+  const int zdim = ((int)q.size(0) + qrows - 1) / qrows;
   dim3 grid(B, n_kv, zdim), block(nw * 64);
   auto stream = c10::hip::getCurrentHIPStream().stream();
-  const bool fp8_cache = k_cache.scalar_type() == torch::kFloat8_e5m2;
-  const int occ = attn_plan::env_v2_occ();
-#define LAUNCH_V2_CT_DW(GG, CT, D, W)                                     \
-  hipLaunchKernelGGL((paged_prefill_v2_kernel<GG, CT, D, W, 8>), grid,    \
-                     block,                                               \
-                     0, stream, (ushort*)out.data_ptr(),                  \
-                     (const ushort*)q.data_ptr(),                         \
-                     (const CT*)k_cache.data_ptr(),                       \
-                     (const CT*)v_cache.data_ptr(),                       \
-                     block_tables.data_ptr<int32_t>(),                    \
-                     query_start_loc.data_ptr<int32_t>(),                 \
-                     seq_lens.data_ptr<int32_t>(), (float)scale, n_kv,    \
-                     max_blocks, q.stride(0))
-#define LAUNCH_V2_NW4(GG, CT)                                             \
-  hipLaunchKernelGGL((paged_prefill_v2_kernel<GG, CT, 0, 2, 4>), grid,    \
-                     block,                                               \
-                     0, stream, (ushort*)out.data_ptr(),                  \
-                     (const ushort*)q.data_ptr(),                         \
-                     (const CT*)k_cache.data_ptr(),                       \
-                     (const CT*)v_cache.data_ptr(),                       \
-                     block_tables.data_ptr<int32_t>(),                    \
-                     query_start_loc.data_ptr<int32_t>(),                 \
-                     seq_lens.data_ptr<int32_t>(), (float)scale, n_kv,    \
-                     max_blocks, q.stride(0))
-#define LAUNCH_V2_CT(GG, CT)                                              \
-  do {                                                                    \
-    switch (dbg_mode & 3) {                                               \
-      case 1: LAUNCH_V2_CT_DW(GG, CT, 1, 2); break;                       \
-      case 2: LAUNCH_V2_CT_DW(GG, CT, 2, 2); break;                       \
-      case 3: LAUNCH_V2_CT_DW(GG, CT, 3, 2); break;                       \
-      default:                                                            \
-        if (occ == 4) LAUNCH_V2_CT_DW(GG, CT, 0, 4);                      \
-        else if (nw == 4) LAUNCH_V2_NW4(GG, CT);                          \
-        else LAUNCH_V2_CT_DW(GG, CT, 0, 2);                               \
-        break;                                                            \
-    }                                                                     \
-  } while (0)
-#define LAUNCH_V2(GG)                                                     \
-  do {                                                                    \
-    if (fp8_cache) {                                                      \
-      LAUNCH_V2_CT(GG, unsigned char);                                    \
-    } else {                                                              \
-      LAUNCH_V2_CT(GG, ushort);                                           \
-    }                                                                     \
-  } while (0)
-  switch (G) {
-    case 1: LAUNCH_V2(1); break;
-    case 2: LAUNCH_V2(2); break;
-    case 4: LAUNCH_V2(4); break;
-    case 8: LAUNCH_V2(8); break;
-    default: TORCH_CHECK(false, "unsupported GQA group size ", G);
-  }
-#undef LAUNCH_V2
-#undef LAUNCH_V2_CT
-#undef LAUNCH_V2_NW4
-#undef LAUNCH_V2_CT_DW
+  const int form =
+      v2_form(attn_plan::env_v2_dbg(), attn_plan::env_v2_occ(), nw);
+  dispatch_int<1, 2, 4, 8>(G, "GQA group size", [&](auto g) {
+    dispatch_bool(s.fp8_cache, [&](auto fp8) {
+      dispatch_int<0, 1, 2, 3, 4, 5>(form, "prefill v2 form", [&](auto fi) {
+        using CT =
+            std::conditional_t<decltype(fp8)::value, unsigned char, ushort>;
+        constexpr V2Form f = kV2Forms[decltype(fi)::value];
+        hipLaunchKernelGGL(
+            (paged_prefill_v2_kernel<decltype(g)::value, CT, f.dbg, f.minw,
+                                     f.nw>),
+            grid, block, 0, stream, (ushort*)out.data_ptr(),
+            (const ushort*)q.data_ptr(), (const CT*)k_cache.data_ptr(),
+            (const CT*)v_cache.data_ptr(), block_tables.data_ptr<int32_t>(),
+            query_start_loc.data_ptr<int32_t>(), seq_lens.data_ptr<int32_t>(),
+            (float)scale, n_kv, max_blocks, q.stride(0));
+      });
+    });
+  });
   HIP_CHECK_KERNEL();
 }
+

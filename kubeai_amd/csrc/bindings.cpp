@@ -15,9 +15,6 @@ void rope_and_cache(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                     torch::Tensor positions, torch::Tensor cos_sin,
                     torch::Tensor k_cache, torch::Tensor v_cache,
                     torch::Tensor slot_mapping);
-void reshape_and_cache_fp8(torch::Tensor k, torch::Tensor v,
-                           torch::Tensor k_cache, torch::Tensor v_cache,
-                           torch::Tensor slot_mapping);
 void reshape_and_cache(torch::Tensor k, torch::Tensor v, torch::Tensor k_cache,
                        torch::Tensor v_cache, torch::Tensor slot_mapping);
 void paged_attention_decode(torch::Tensor out, torch::Tensor q,
@@ -110,9 +107,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope", &rope, "NeoX rotary embedding, in-place q/k");
   m.def("rope_and_cache", &rope_and_cache,
         "rotary embedding (in-place q/k) fused with the paged KV cache write");
-  m.def("reshape_and_cache", &reshape_and_cache, "paged KV cache write");
-  m.def("reshape_and_cache_fp8", &reshape_and_cache_fp8,
-        "paged KV cache write, fp8 e5m2 cache");
+  m.def("reshape_and_cache", &reshape_and_cache,
+        "paged KV cache write (bf16 or fp8 e5m2 cache)");
   m.def("paged_attention_decode", &paged_attention_decode,
         "paged attention, one query token per seq");
   m.def("paged_attention_decode_fp8", &paged_attention_decode_fp8,

@@ -110,6 +110,28 @@ DEV_INLINE unsigned char f32_to_e5m2(float x) {
   return (unsigned char)__hip_cvt_float_to_fp8(x, __HIP_SATFINITE, __HIP_E5M2);
 }
 
+// 8 bf16 values -> 8 packed e5m2 bytes (the inverse staging unit: what a
+// cache write stores for one 16 B vector of a K/V row). rope_and_cache_kernel
+// and the decode kernel's RAW store spell the same loop inline: through this
+// call the compiler schedules them differently
+// (profiles/r06_launch_dispatch.md).
+DEV_INLINE uint64_t bf16x8_to_e5m2x8(const ushort8 v) {
+  uint64_t out = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    out |= (uint64_t)f32_to_e5m2(bf16_to_f32((ushort)v[j])) << (8 * j);
+  return out;
+}
+
+// ---------------- paged KV cache ----------------
+// Element offset of the row of `slot` for kv head `head` in a cache laid out
+// [num_blocks, n_kv, bs, hd]: block slot / bs, row slot % bs.
+DEV_INLINE int64_t cache_row_offset(const int64_t slot, const int bs,
+                                    const int n_kv, const int head,
+                                    const int hd) {
+  return (((slot / bs) * n_kv + head) * bs + slot % bs) * hd;
+}
+
 // ---------------- NeoX rotary pair ----------------
 // Rotates the pair (x1, x2) = (x[i], x[i + hd/2]) by (c, s) and rounds to
 // bf16. Every rotary kernel goes through this one expression, and the

@@ -15,7 +15,10 @@
 // (views into the fused qkv buffer, or separately contiguous tensors).
 #include <torch/extension.h>
 
+#include <type_traits>
+
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -53,13 +56,15 @@ __global__ void rope_and_cache_kernel(
     const int h = head - n_q - n_kv;
     const ushort8* src =
         reinterpret_cast<const ushort8*>(v + tok * v_stride + (int64_t)h * hd);
-    CT* dst = v_cache + (((slot / bs) * n_kv + h) * bs + slot % bs) * hd;
+    CT* dst = v_cache + cache_row_offset(slot, bs, n_kv, h, hd);
     const int nvec = hd / 8;
     for (int i = lane; i < nvec; i += WAVE_SIZE) {
       const ushort8 vv = src[i];
       if constexpr (sizeof(CT) == 2) {
         reinterpret_cast<ushort8*>(dst)[i] = vv;
       } else {
+        // bf16x8_to_e5m2x8, spelled out: through the helper the compiler
+        // schedules this kernel differently (profiles/r06_launch_dispatch.md)
         uint64_t vo = 0;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -81,8 +86,7 @@ __global__ void rope_and_cache_kernel(
   if (is_k) {
     const int64_t slot = slot_mapping[tok];
     if (slot >= 0)
-      dst = k_cache +
-            (((slot / bs) * n_kv + (head - n_q)) * bs + slot % bs) * hd;
+      dst = k_cache + cache_row_offset(slot, bs, n_kv, head - n_q, hd);
   }
   for (int i = lane; i < half; i += WAVE_SIZE) {
     const float c = cs[i];
@@ -138,20 +142,17 @@ void rope_and_cache(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   const int64_t total_waves = (int64_t)T * (n_q + 2 * n_kv);
   const int waves_per_block = 4;  // 256 threads
   const int64_t blocks = (total_waves + waves_per_block - 1) / waves_per_block;
-#define LAUNCH_RC(CT)                                                        \
-  hipLaunchKernelGGL(                                                        \
-      (rope_and_cache_kernel<CT>), dim3((uint32_t)blocks),                   \
-      dim3(waves_per_block * WAVE_SIZE), 0,                                  \
-      c10::hip::getCurrentHIPStream().stream(), (ushort*)q.data_ptr(),       \
-      (ushort*)k.data_ptr(), (const ushort*)v.data_ptr(),                    \
-      (CT*)k_cache.data_ptr(), (CT*)v_cache.data_ptr(),                      \
-      positions.data_ptr<int32_t>(), cos_sin.data_ptr<float>(),              \
-      slot_mapping.data_ptr<int64_t>(), n_q, n_kv, hd, bs, (int64_t)T,       \
-      q.stride(0), k.stride(0), v.stride(0))
-  if (fp8_cache)
-    LAUNCH_RC(unsigned char);
-  else
-    LAUNCH_RC(ushort);
-#undef LAUNCH_RC
+  dispatch_bool(fp8_cache, [&](auto fp8) {
+    using CT = std::conditional_t<decltype(fp8)::value, unsigned char, ushort>;
+    hipLaunchKernelGGL(
+        rope_and_cache_kernel<CT>, dim3((uint32_t)blocks),
+        dim3(waves_per_block * WAVE_SIZE), 0,
+        c10::hip::getCurrentHIPStream().stream(), (ushort*)q.data_ptr(),
+        (ushort*)k.data_ptr(), (const ushort*)v.data_ptr(),
+        (CT*)k_cache.data_ptr(), (CT*)v_cache.data_ptr(),
+        positions.data_ptr<int32_t>(), cos_sin.data_ptr<float>(),
+        slot_mapping.data_ptr<int64_t>(), n_q, n_kv, hd, bs, (int64_t)T,
+        q.stride(0), k.stride(0), v.stride(0));
+  });
   HIP_CHECK_KERNEL();
 }

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -200,9 +201,6 @@ __launch_bounds__(kThreads) __global__ void row_fp8_kernel(
 //          (profiles/r03_decode_small_kernels.md): twice the loads in
 //          flight.
 enum class RowPolicy { kNorm, kMax };
-
-template <int N>
-using Int = std::integral_constant<int, N>;
 
 template <RowPolicy kPolicy, typename Launch>
 void dispatch_row(const int nvec, Launch&& launch) {

@@ -51,6 +51,85 @@ def _rms_head(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
     return (xf * w.float()).to(x.dtype)
 
 
+def paged_attention_step(
+    q: torch.Tensor,  # [T, n_q, hd], unrotated
+    k: torch.Tensor,  # [T, n_kv, hd], unrotated
+    v: torch.Tensor,  # [T, n_kv, hd]
+    fb: ForwardBatch,
+    kv_cache: tuple[torch.Tensor, torch.Tensor],
+    cos_sin: torch.Tensor,
+    *,
+    scale: float,
+    window: int,
+    softcap: float,
+    fp8_out: bool,
+):
+    """Rope, KV-cache write and paged attention of one layer over the batch
+    (decode rows first, then prefill rows). Returns the attention output
+    flattened to [T, n_q * hd], or its fp8 row quantization (fp8, row
+    scales), the o_proj input of the fused-fp8 path, when fp8_out is set.
+    q, k and v may be row-strided views into the fused qkv buffer — the HIP
+    kernels take a row stride per tensor."""
+    k_cache, v_cache = kv_cache
+    T = q.shape[0]
+    out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    nd = fb.n_decode
+    if fb.n_prefill == 0 and nd == T and nd > 0 and q.is_cuda:
+        # pure-decode step: nothing after attention reads the rotated
+        # q/k, so the decode kernel rotates them and writes the new K/V
+        # rows itself (no rope launch). On the fp8 path its merge step
+        # also emits the o_proj input (fp8 + row scales), no separate
+        # quant_fp8 launch.
+        res = ops.rope_cache_attention_decode(
+            q,
+            k,
+            v,
+            fb.positions,
+            cos_sin,
+            k_cache,
+            v_cache,
+            fb.slot_mapping,
+            fb.decode_block_tables,
+            fb.decode_seq_lens,
+            scale,
+            out=out,
+            window=window,
+            softcap=softcap,
+            fp8_out=fp8_out,
+        )
+        return res[1:] if fp8_out else out.view(T, -1)
+    q, k = ops.rope_and_cache(
+        q, k, v, fb.positions, cos_sin, k_cache, v_cache, fb.slot_mapping
+    )
+    if nd > 0:
+        ops.paged_attention_decode(
+            q[:nd],
+            k_cache,
+            v_cache,
+            fb.decode_block_tables,
+            fb.decode_seq_lens,
+            scale,
+            out=out[:nd],
+            window=window,
+            softcap=softcap,
+        )
+    if fb.n_prefill > 0:
+        ops.paged_attention_prefill(
+            q[nd:],
+            k_cache,
+            v_cache,
+            fb.prefill_block_tables,
+            fb.prefill_query_start_loc,
+            fb.prefill_seq_lens,
+            scale,
+            out=out[nd:],
+            window=window,
+            softcap=softcap,
+        )
+    attn_flat = out.view(T, -1)
+    return ops.quant_fp8(attn_flat) if fp8_out else attn_flat
+
+
 class Attention(nn.Module):
     def __init__(self, cfg: ModelArchConfig, layer_idx: int):
         super().__init__()
@@ -98,11 +177,9 @@ class Attention(nn.Module):
         # fused producer kernel (DecoderLayer fp8 path)
         if fp8_in:
             xq, xs = x
-            T = xq.shape[0]
             qkv = self.qkv_proj.forward_quantized(xq, xs)
             lm = None
         else:
-            T = x.shape[0]
             qkv = self.qkv_proj(x)
             lm = getattr(self, "_lora_manager", None)
             if lm is not None and lm.active and fb.lora_ids is not None:
@@ -124,71 +201,13 @@ class Attention(nn.Module):
         if isinstance(cos_sin, tuple):
             # (global, local) caches — gemma3 dual rope bases
             cos_sin = cos_sin[0] if self.is_global else cos_sin[1]
-        k_cache, v_cache = kv_cache
-        out = torch.empty(
-            (T, self.n_q, self.hd), dtype=qkv.dtype, device=qkv.device
+        attn = paged_attention_step(
+            q, k, v, fb, kv_cache, cos_sin, scale=self.scale,
+            window=self.window, softcap=self.softcap, fp8_out=fp8_in,
         )
-        nd = fb.n_decode
-        if fb.n_prefill == 0 and nd == T and nd > 0 and qkv.is_cuda:
-            # pure-decode step: nothing after attention reads the rotated
-            # q/k, so the decode kernel rotates them and writes the new K/V
-            # rows itself (no rope launch). On the fp8 path its merge step
-            # also emits the o_proj input (fp8 + row scales), no separate
-            # quant_fp8 launch.
-            res = ops.rope_cache_attention_decode(
-                q,
-                k,
-                v,
-                fb.positions,
-                cos_sin,
-                k_cache,
-                v_cache,
-                fb.slot_mapping,
-                fb.decode_block_tables,
-                fb.decode_seq_lens,
-                self.scale,
-                out=out,
-                window=self.window,
-                softcap=self.softcap,
-                fp8_out=fp8_in,
-            )
-            if fp8_in:
-                _, a8, ascale = res
-                return self.o_proj.forward_quantized(a8, ascale)
-            return self._o_proj_bf16(out.view(T, -1), fb, lm)
-        q, k = ops.rope_and_cache(
-            q, k, v, fb.positions, cos_sin, k_cache, v_cache, fb.slot_mapping
-        )
-        if nd > 0:
-            ops.paged_attention_decode(
-                q[:nd],
-                k_cache,
-                v_cache,
-                fb.decode_block_tables,
-                fb.decode_seq_lens,
-                self.scale,
-                out=out[:nd],
-                window=self.window,
-                softcap=self.softcap,
-            )
-        if fb.n_prefill > 0:
-            ops.paged_attention_prefill(
-                q[nd:],
-                k_cache,
-                v_cache,
-                fb.prefill_block_tables,
-                fb.prefill_query_start_loc,
-                fb.prefill_seq_lens,
-                self.scale,
-                out=out[nd:],
-                window=self.window,
-                softcap=self.softcap,
-            )
-        attn_flat = out.view(T, -1)
         if fp8_in:
-            a8, ascale = ops.quant_fp8(attn_flat)
-            return self.o_proj.forward_quantized(a8, ascale)
-        return self._o_proj_bf16(attn_flat, fb, lm)
+            return self.o_proj.forward_quantized(*attn)
+        return self._o_proj_bf16(attn, fb, lm)
 
     def _o_proj_bf16(self, attn_flat, fb: ForwardBatch, lm) -> torch.Tensor:
         result = self.o_proj(attn_flat)

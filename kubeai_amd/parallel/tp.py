@@ -29,7 +29,7 @@ import torch.nn.functional as F
 from kubeai_amd import ops
 from kubeai_amd.engine.batch import ForwardBatch
 from kubeai_amd.models.config import ModelArchConfig
-from kubeai_amd.models.llama import EngineLinear
+from kubeai_amd.models.llama import EngineLinear, paged_attention_step
 
 
 class TPGroup:
@@ -147,10 +147,8 @@ class TPAttention(nn.Module):
         # producer (TPDecoderLayer fp8 path, same as models/llama.py)
         if fp8_in:
             xq, xs = x
-            T = xq.shape[0]
             qkv = self.qkv_proj.forward_quantized(xq, xs)
         else:
-            T = x.shape[0]
             qkv = self.qkv_proj(x)
         q, k, v = qkv.split(
             [self.n_q * self.hd, self.n_kv * self.hd, self.n_kv * self.hd], dim=-1
@@ -158,46 +156,14 @@ class TPAttention(nn.Module):
         q = q.unflatten(-1, (self.n_q, self.hd))
         k = k.unflatten(-1, (self.n_kv, self.hd))
         v = v.unflatten(-1, (self.n_kv, self.hd))
-        k_cache, v_cache = kv_cache
-        out = torch.empty(
-            (T, self.n_q, self.hd), dtype=qkv.dtype, device=qkv.device
+        attn = paged_attention_step(
+            q, k, v, fb, kv_cache, cos_sin, scale=self.scale,
+            window=self.window, softcap=0.0, fp8_out=fp8_in,
         )
-        nd = fb.n_decode
-        if fb.n_prefill == 0 and nd == T and nd > 0 and qkv.is_cuda:
-            # pure-decode step: rope and the cache write happen inside the
-            # decode kernel; on the fp8 path the merge step emits the o_proj
-            # input (same as models/llama.py)
-            res = ops.rope_cache_attention_decode(
-                q, k, v, fb.positions, cos_sin, k_cache, v_cache,
-                fb.slot_mapping, fb.decode_block_tables, fb.decode_seq_lens,
-                self.scale, out=out, window=getattr(self, "window", 0),
-                fp8_out=fp8_in,
-            )
-            if fp8_in:
-                _, a8, ascale = res
-                return self.o_proj.forward_quantized(a8, ascale)  # partial sum
-            return self.o_proj(out.view(T, -1))  # partial; layer all-reduces
-        q, k = ops.rope_and_cache(
-            q, k, v, fb.positions, cos_sin, k_cache, v_cache, fb.slot_mapping
-        )
-        if nd > 0:
-            ops.paged_attention_decode(
-                q[:nd], k_cache, v_cache,
-                fb.decode_block_tables, fb.decode_seq_lens, self.scale,
-                out=out[:nd], window=getattr(self, "window", 0),
-            )
-        if fb.n_prefill > 0:
-            ops.paged_attention_prefill(
-                q[nd:], k_cache, v_cache,
-                fb.prefill_block_tables, fb.prefill_query_start_loc,
-                fb.prefill_seq_lens, self.scale,
-                out=out[nd:], window=getattr(self, "window", 0),
-            )
-        attn_flat = out.view(T, -1)
+        # o_proj gives this rank's partial sum; the layer all-reduces
         if fp8_in:
-            a8, ascale = ops.quant_fp8(attn_flat)
-            return self.o_proj.forward_quantized(a8, ascale)  # partial sum
-        return self.o_proj(attn_flat)  # partial; layer all-reduces
+            return self.o_proj.forward_quantized(*attn)
+        return self.o_proj(attn)
 
 
 class TPMLP(nn.Module):

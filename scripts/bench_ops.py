@@ -125,13 +125,15 @@ def main():
 
     # ---- cache write ----
     Tc = 4096
-    kc = torch.zeros(Tc // 16 + 1, 8, 16, 128, dtype=torch.bfloat16, device=dev)
-    vc = torch.zeros_like(kc)
     kt = torch.randn(Tc, 8, 128, dtype=torch.bfloat16, device=dev)
     vt = torch.randn_like(kt)
     slots = torch.arange(Tc, dtype=torch.int64, device=dev)
-    us = timeit(lambda: ops.reshape_and_cache(kt, vt, kc, vc, slots))
-    report("reshape_and_cache 4096tok", us, bytes_moved=4 * kt.numel() * 2)
+    for name, dt in (("", torch.bfloat16), (" e5m2", torch.float8_e5m2)):
+        kc = torch.zeros(Tc // 16 + 1, 8, 16, 128, device=dev).to(dt)
+        vc = torch.zeros_like(kc)
+        us = timeit(lambda: ops.reshape_and_cache(kt, vt, kc, vc, slots))
+        report(f"reshape_and_cache 4096tok{name}", us,
+               bytes_moved=2 * kt.numel() * (2 + kc.element_size()))
 
 
 if __name__ == "__main__":

@@ -212,6 +212,26 @@ def test_decode(hd, G, cache_dtype, family):
 
 
 @pytest.mark.parametrize("cache_dtype", DTYPES)
+@pytest.mark.parametrize("G", [2, 5, 6])
+@pytest.mark.parametrize("hd", [128, 256])
+def test_decode_other_group_sizes(hd, G, cache_dtype):
+    """The remaining instantiated group sizes (test_decode and the hd 256
+    cases cover 1, 4, 8 and G = 2 at hd 256): a launcher that routed one of
+    them to a neighbouring instantiation would read the wrong heads."""
+    B = len(_DEC_LENS)
+    c = make_case("randn", [1] * B, [L - 1 for L in _DEC_LENS], 2 * G, 2,
+                  hd=hd, cache_dtype=cache_dtype, device=DEV, seed=21)
+    _check_decode(c, 16, f"decode/hd{hd}/G{G}/randn")
+
+
+def test_decode_rejects_unsupported_group_size():
+    """G = 3 has no instantiation: a host error before any launch."""
+    c = make_case("randn", [1], [16], 3, 1, device=DEV, seed=27)
+    with pytest.raises(RuntimeError, match="unsupported GQA group size"):
+        _run_decode(c)
+
+
+@pytest.mark.parametrize("cache_dtype", DTYPES)
 @pytest.mark.parametrize("hd", [128, 256])
 def test_decode_window_ramp_down(hd, cache_dtype):
     """Window 48 with the mass on key L - 48; L = 48 and 49 straddle the

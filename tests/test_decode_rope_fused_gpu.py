@@ -142,7 +142,9 @@ def _check(
     return out_b
 
 
-HEADS = [(32, 8, 128), (8, 1, 128), (8, 8, 128), (8, 4, 256)]
+# G = 4, 8, 1, 2, then the other instantiated group sizes: 2 at hd 128, 5, 6
+HEADS = [(32, 8, 128), (8, 1, 128), (8, 8, 128), (8, 4, 256),
+         (4, 2, 128), (10, 2, 128), (12, 2, 256)]
 
 
 @pytest.mark.parametrize("cache_dtype", [torch.bfloat16, torch.float8_e5m2])

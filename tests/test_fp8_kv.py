@@ -1,6 +1,6 @@
 """fp8(e5m2) KV cache: CPU semantics + conversion-spec tests.
 
-The GPU kernels (reshape_and_cache_fp8 + fp8-templated attention) are
+The GPU kernels (reshape_and_cache + attention, templated on the cache type) are
 compiled for gfx950 and dispatched when the cache dtype is float8_e5m2;
 device validation is scheduled for round 2 (NOTES.md) — the feature stays
 off by default (kv_cache_dtype="auto")."""

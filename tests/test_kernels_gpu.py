@@ -79,6 +79,28 @@ def test_reshape_and_cache():
     torch.testing.assert_close(vc, vc_ref)
 
 
+def test_reshape_and_cache_e5m2_strided():
+    """e5m2 cache through the one entry point, byte for byte the reference's
+    cast; k and v are row-strided views of one buffer, one token dropped."""
+    T, nkv, hd, nb, bs = 5, 2, 128, 2, 16
+    kv = torch.randn(T, 2 * nkv * hd, dtype=torch.bfloat16, device=DEV)
+    k = kv[:, : nkv * hd].unflatten(-1, (nkv, hd))
+    v = kv[:, nkv * hd :].unflatten(-1, (nkv, hd))
+    assert k.stride(0) == v.stride(0) == 2 * nkv * hd
+    slots = torch.tensor([17, 3, -1, 31, 0], dtype=torch.int64, device=DEV)
+    kc0 = torch.randn(nb, nkv, bs, hd, device=DEV).to(torch.float8_e5m2)
+    vc0 = torch.randn(nb, nkv, bs, hd, device=DEV).to(torch.float8_e5m2)
+    kc, vc = kc0.clone(), vc0.clone()
+    ops.reshape_and_cache(k, v, kc, vc, slots)
+    kc_ref, vc_ref = kc0.cpu(), vc0.cpu()
+    ref.reshape_and_cache(k.cpu(), v.cpu(), kc_ref, vc_ref, slots.cpu())
+    assert torch.equal(kc.cpu().view(torch.uint8), kc_ref.view(torch.uint8))
+    assert torch.equal(vc.cpu().view(torch.uint8), vc_ref.view(torch.uint8))
+    # four rows of each cache were written, the rest is as it was
+    changed = (kc.view(torch.uint8) != kc0.view(torch.uint8)).any(-1)
+    assert int(changed.sum()) == 4 * nkv
+
+
 def _rand_cache(nb, nkv, bs, hd):
     kc = torch.randn(nb, nkv, bs, hd, dtype=torch.bfloat16, device=DEV)
     vc = torch.randn(nb, nkv, bs, hd, dtype=torch.bfloat16, device=DEV)
