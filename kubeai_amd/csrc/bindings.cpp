@@ -43,6 +43,13 @@ void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
 void silu_and_mul(torch::Tensor out, torch::Tensor x);
 void gelu_and_mul(torch::Tensor out, torch::Tensor x);
 void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w);
+// W4A16 (int4_gemm.hip); (qp, sp, zp) is Int4Weight's packed layout
+void int4_dequant(torch::Tensor out, torch::Tensor qp, torch::Tensor sp,
+                  torch::Tensor zp, int64_t N, int64_t K, int64_t group);
+void int4_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor qp,
+               torch::Tensor sp, torch::Tensor zp, int64_t N, int64_t K,
+               int64_t group);
+int64_t int4_gemm_tiles(int64_t N, int64_t M);
 void greedy_sample(torch::Tensor out, torch::Tensor logits);
 void gumbel_sample(torch::Tensor out, torch::Tensor logits,
                    torch::Tensor temperature, torch::Tensor seeds,
@@ -121,6 +128,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelu_and_mul", &gelu_and_mul, "GeGLU tanh-gelu(gate)*up");
   m.def("silu_and_mul", &silu_and_mul, "SwiGLU activation");
   m.def("skinny_gemm", &skinny_gemm, "weight-streaming GEMM for M<=64");
+  m.def("int4_dequant", &int4_dequant,
+        "packed int4 weight -> bf16 [N, K], bit-equal to Int4Weight.dequant()");
+  m.def("int4_gemm", &int4_gemm,
+        "fused dequant + GEMM over a packed int4 weight, M <= 64");
+  m.def("int4_gemm_tiles", &int4_gemm_tiles,
+        "16-column tiles per workgroup int4_gemm launches with",
+        pybind11::arg("N"), pybind11::arg("M"));
   m.def("greedy_sample", &greedy_sample, "argmax sampling");
   m.def("gumbel_sample", &gumbel_sample, "temperature sampling (hash RNG)");
   m.def("rmsnorm_fp8", &rmsnorm_fp8, "rmsnorm with fused fp8 row quant");

@@ -35,7 +35,11 @@ class EngineConfig:
     max_num_batched_tokens: int = 8192
     max_model_len: int = 8192
     enable_prefix_caching: bool = True
-    quantization: Optional[str] = None  # "fp8" => W8A8 dynamic (quant.py)
+    # "fp8"  => W8A8 dynamic (quant.py)
+    # "int4" => W4A16 (quant_int4.py): AWQ-gemm checkpoints are served from
+    #           their packed codes, float weights are quantized round-to-
+    #           nearest (g=128); lm_head stays bf16; not with tensor parallelism
+    quantization: Optional[str] = None
     # "auto" = model dtype; "fp8_e5m2" halves KV bytes + doubles capacity
     kv_cache_dtype: str = "auto"
     enable_graphs: bool = True  # hipGraph capture for pure-decode steps

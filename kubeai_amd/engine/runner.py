@@ -122,6 +122,13 @@ class ModelRunner:
         self._json_validators: dict = {}
         self._sampling_cache: dict = {}
         torch.manual_seed(seed)
+        if quantization == "int4" and tp_group is not None:
+            # packed int4 tensors have no sharding rule yet: reject loudly
+            # rather than shard wrongly
+            raise NotImplementedError(
+                "quantization='int4' is not implemented with tensor "
+                "parallelism"
+            )
         if tp_group is not None:
             from kubeai_amd.parallel.tp import TPLlamaForCausalLM
 
@@ -160,8 +167,22 @@ class ModelRunner:
             else:
                 from kubeai_amd.models.loader import load_weights
 
-                load_weights(self.model, model_path, vision=self.vision)
+                # int4: an AWQ checkpoint's packed linears are installed as
+                # they are (no dequantize + re-quantize round trip)
+                load_weights(
+                    self.model, model_path, vision=self.vision,
+                    keep_int4=quantization == "int4",
+                )
         self.quantization = quantization
+        if quantization == "int4":
+            # whatever the load left in bf16 (float checkpoints, presets) is
+            # quantized round-to-nearest; lm_head stays bf16
+            from .quant_int4 import Int4Linear, convert_to_int4
+
+            convert_to_int4(self.model)
+            assert any(
+                isinstance(m, Int4Linear) for m in self.model.modules()
+            ), "no linear layers converted to int4"
         if quantization == "fp8":
             # on CPU the Fp8Linear dequant fallback keeps the same
             # semantics (tests); the fast _scaled_mm path needs the GPU

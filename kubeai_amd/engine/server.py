@@ -1248,7 +1248,7 @@ def _tp_worker_main(rank: int, world: int, port: int, cfg: EngineConfig) -> None
     dist.destroy_process_group()
 
 
-def main():
+def build_arg_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
     p.add_argument("--model", required=True, help="preset name or model dir")
     p.add_argument("--served-model-name", default=None)
@@ -1261,14 +1261,20 @@ def main():
     p.add_argument("--num-gpu-blocks", type=int, default=None)
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8_e5m2"],
                    default="auto")
-    p.add_argument("--quantization", choices=["fp8"], default=None,
-                   help="fp8 = W8A8 dynamic with fused activation quant")
+    p.add_argument("--quantization", choices=["fp8", "int4"], default=None,
+                   help="fp8 = W8A8 dynamic with fused activation quant; "
+                        "int4 = W4A16, AWQ checkpoints served packed "
+                        "(float checkpoints are quantized round-to-nearest)")
     p.add_argument("--enable-lora", action="store_true")
     p.add_argument("--tensor-parallel-size", type=int, default=1)
     p.add_argument("--task", choices=["generate", "transcribe", "embed"],
                    default=None,
                    help="auto: whisper-* -> transcribe, bert/bge/e5 -> embed")
-    args = p.parse_args()
+    return p
+
+
+def main():
+    args = build_arg_parser().parse_args()
     base = os.path.basename(args.model.rstrip("/")).lower()
     if args.task:
         task = args.task

@@ -56,12 +56,17 @@ def _awq_dequant(qweight, qzeros, scales) -> torch.Tensor:
     return ((iw - z) * s).t().contiguous().to(torch.bfloat16)
 
 
-def iter_safetensors(model_dir: str) -> Iterator[tuple[str, torch.Tensor]]:
+def iter_safetensors(
+    model_dir: str, keep_int4: bool = False
+) -> Iterator[tuple[str, torch.Tensor]]:
     """Yield (name, tensor) over all shards; pre-quantized fp8 checkpoints
     (e.g. Llama-3.1-*-FP8: fp8 weights + per-tensor `weight_scale`) are
     dequantized on the fly so callers always see plain float weights.
     Unsupported quant formats (AWQ/GPTQ packed ints) raise instead of
-    silently producing garbage."""
+    silently producing garbage.
+
+    keep_int4: AWQ-gemm groups are yielded as engine.quant_int4.Int4Weight
+    (the checkpoint's own codes, repacked) instead of dequantized bf16."""
     from safetensors import safe_open
 
     files = sorted(glob.glob(os.path.join(model_dir, "*.safetensors")))
@@ -103,11 +108,20 @@ def iter_safetensors(model_dir: str) -> Iterator[tuple[str, torch.Tensor]]:
                             "bf16/fp16, fp8(+weight_scale), or AWQ-INT4 "
                             "gemm checkpoints"
                         )
-                    yield pre + ".weight", _awq_dequant(
+                    group = (
                         sf.get_tensor(key),
                         sf.get_tensor(pre + ".qzeros"),
                         sf.get_tensor(pre + ".scales"),
                     )
+                    if keep_int4:
+                        from kubeai_amd.engine.quant_int4 import Int4Weight
+
+                        try:
+                            yield pre + ".weight", Int4Weight.from_awq(*group)
+                        except ValueError as e:
+                            raise ValueError(f"{pre}: {e}") from None
+                    else:
+                        yield pre + ".weight", _awq_dequant(*group)
                     continue
                 if any(key.endswith("." + s) for s in _UNSUPPORTED_QUANT_KEYS):
                     raise ValueError(
@@ -148,10 +162,15 @@ def _strip(name: str) -> str:
     return name
 
 
-def load_weights_tp(model, model_dir: str, vision=None) -> int:
+def load_weights_tp(model, model_dir: str, vision=None, keep_int4: bool = False) -> int:
     """Load HF weights into TPLlamaForCausalLM: every rank reads the full
     tensors and keeps its shard (same slicing as parallel/tp.py init).
     The vision tower (llava) is replicated on every rank, not sharded."""
+    if keep_int4:
+        raise NotImplementedError(
+            "packed int4 weights are not sharded: tensor-parallel int4 is "
+            "not implemented"
+        )
     cfg = model.cfg
     tp = model.tp
     hd = cfg.head_dim
@@ -270,17 +289,72 @@ def load_weights_tp(model, model_dir: str, vision=None) -> int:
     return len(filled)
 
 
-def load_weights(model, model_dir: str, vision=None) -> int:
+def load_weights(model, model_dir: str, vision=None, keep_int4: bool = False) -> int:
     """Load HF weights into LlamaForCausalLM (dense or MoE). Returns the
     number of engine parameters filled; raises if any stays unset.
 
     vision: optional models/vision.py VisionTower — llava checkpoints
     route their vision_tower.* / multi_modal_projector.* tensors there
-    (HF llava nests the text model under language_model.*)."""
+    (HF llava nests the text model under language_model.*).
+
+    keep_int4: the packed linears of an AWQ-gemm checkpoint are not
+    dequantized; q/k/v and gate/up are joined with Int4Weight.cat and each
+    target is installed as an Int4Linear, so the served weights are exactly
+    the checkpoint's codes. Packed MoE experts raise NotImplementedError."""
+    from kubeai_amd.engine.quant_int4 import Int4Linear, Int4Weight
+
     cfg = model.cfg
     hd, nq, nkv = cfg.head_dim, cfg.num_attention_heads, cfg.num_key_value_heads
     params = dict(model.named_parameters())
     filled: set[str] = set()
+
+    def install_int4(parent: str, attr: str, parts: list) -> None:
+        mod = model.get_submodule(parent)
+        old = getattr(mod, attr)
+        target = f"{parent}.{attr}"
+        if not all(isinstance(p, Int4Weight) for p in parts):
+            raise ValueError(
+                f"{target}: packed int4 and float tensors cannot be fused"
+            )
+        try:
+            w = Int4Weight.cat(parts)
+        except ValueError as e:
+            raise ValueError(f"{target}: {e}") from None
+        if (w.N, w.K) != tuple(old.weight.shape):
+            raise ValueError(
+                f"{target}: shape {(w.N, w.K)} != {tuple(old.weight.shape)}"
+            )
+        setattr(mod, attr, Int4Linear(w.to(old.weight.device), old.bias))
+        filled.add(target + ".weight")
+
+    def put_int4(layer: int, rest: str, w) -> None:
+        pre = f"layers.{layer}"
+        direct = {
+            "self_attn.qkv_proj.weight": ("self_attn", "qkv_proj"),
+            "self_attn.o_proj.weight": ("self_attn", "o_proj"),
+            "mlp.gate_up_proj.weight": ("mlp", "gate_up_proj"),
+            "mlp.down_proj.weight": ("mlp", "down_proj"),
+        }
+        fused = {
+            "self_attn.q_proj.weight": ("qkv", "q"),
+            "self_attn.k_proj.weight": ("qkv", "k"),
+            "self_attn.v_proj.weight": ("qkv", "v"),
+            "mlp.gate_proj.weight": ("gu", "gate"),
+            "mlp.up_proj.weight": ("gu", "up"),
+        }
+        if rest in direct:
+            sub, attr = direct[rest]
+            install_int4(f"{pre}.{sub}", attr, [w])
+        elif rest in fused:
+            kind, part = fused[rest]
+            pending.setdefault(f"{kind}.{layer}", {})[part] = w
+            fuse_qkv(layer) if kind == "qkv" else fuse_gate_up(layer, None)
+        else:
+            raise NotImplementedError(
+                f"{pre}.{rest}: packed int4 tensors are served only for the "
+                "dense qkv/o/gate_up/down projections (packed MoE-expert "
+                "checkpoints are not supported)"
+            )
 
     def put(target: str, tensor: torch.Tensor) -> None:
         p = params[target]
@@ -296,9 +370,13 @@ def load_weights(model, model_dir: str, vision=None) -> int:
     def fuse_qkv(layer: int) -> None:
         ps = pending.get(f"qkv.{layer}", {})
         if len(ps) == 3:
+            parts = [ps["q"], ps["k"], ps["v"]]
+            if any(isinstance(p, Int4Weight) for p in parts):
+                install_int4(f"layers.{layer}.self_attn", "qkv_proj", parts)
+                return
             put(
                 f"layers.{layer}.self_attn.qkv_proj.weight",
-                torch.cat([ps["q"], ps["k"], ps["v"]], dim=0),
+                torch.cat(parts, dim=0),
             )
 
     def fuse_qkv_bias(layer: int) -> None:
@@ -313,14 +391,32 @@ def load_weights(model, model_dir: str, vision=None) -> int:
         key = f"gu.{layer}" + ("" if expert is None else f".{expert}")
         ps = pending.get(key, {})
         if len(ps) == 2:
+            parts = [ps["gate"], ps["up"]]
+            if expert is None and any(isinstance(p, Int4Weight) for p in parts):
+                install_int4(f"layers.{layer}.mlp", "gate_up_proj", parts)
+                return
             tgt = (
                 f"layers.{layer}.mlp.gate_up_proj.weight"
                 if expert is None
                 else f"layers.{layer}.mlp.experts.{expert}.gate_up_proj.weight"
             )
-            put(tgt, torch.cat([ps["gate"], ps["up"]], dim=0))
+            put(tgt, torch.cat(parts, dim=0))
 
-    for name, w in iter_safetensors(model_dir):
+    for name, w in iter_safetensors(model_dir, keep_int4=keep_int4):
+        if isinstance(w, Int4Weight):
+            n = _strip(name)
+            parts = n.split(".")
+            if "layers" not in parts:
+                raise NotImplementedError(
+                    f"{name}: packed int4 tensors are served only for the "
+                    "decoder projections"
+                )
+            put_int4(
+                int(parts[parts.index("layers") + 1]),
+                ".".join(parts[parts.index("layers") + 2 :]),
+                w,
+            )
+            continue
         if name.startswith(("vision_tower.", "multi_modal_projector.")):
             if vision is not None and not vision.load_hf_tensor(name, w):
                 raise ValueError(f"unrecognized vision tensor {name}")

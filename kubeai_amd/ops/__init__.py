@@ -268,6 +268,68 @@ def linear(x, weight):
     return torch.nn.functional.linear(x, weight)
 
 
+# ---------------- int4 (W4A16) ----------------
+# `w` below is an engine.quant_int4.Int4Weight (packed qp/sp/zp + N, K, group).
+
+# Largest M the fused dequant-GEMM kernel takes; above it int4_linear runs
+# int4_dequant + the library GEMM. See docs/kernels.md for how it is set.
+INT4_M_FUSED = int(os.environ.get("KUBEAI_INT4_M_FUSED", "64"))
+
+# device -> flat bf16 buffer the large-M route dequantizes into. Grown only by
+# int4_reserve_workspace, which every GPU Int4Weight calls at construction:
+# that route can run under graph capture and must not allocate there.
+_INT4_WORKSPACE: dict = {}
+
+
+def int4_reserve_workspace(device, numel: int) -> None:
+    device = torch.device(device)
+    ws = _INT4_WORKSPACE.get(device)
+    if ws is None or ws.numel() < numel:
+        _INT4_WORKSPACE[device] = torch.empty(
+            numel, dtype=torch.bfloat16, device=device
+        )
+
+
+def int4_dequant(w, out=None):
+    """Packed int4 weight -> bf16 [N, K], bit-identical to w.dequant()."""
+    if not w.qp.is_cuda:
+        res = w.dequant()
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+    _require_ext()
+    if out is None:
+        out = torch.empty((w.N, w.K), dtype=torch.bfloat16, device=w.qp.device)
+    _C.int4_dequant(out, w.qp, w.sp, w.zp, w.N, w.K, w.group)
+    return out
+
+
+def int4_linear(x, w):
+    """y[M, N] = x[M, K] @ w.dequant()^T, bf16, fp32 accumulation. x may be a
+    row-strided view with a contiguous last dimension."""
+    if not x.is_cuda:
+        return torch.nn.functional.linear(x, w.dequant())
+    _require_ext()
+    if x.dim() != 2:
+        return int4_linear(x.reshape(-1, x.shape[-1]), w).view(*x.shape[:-1], w.N)
+    M = x.shape[0]
+    if 1 <= M <= min(INT4_M_FUSED, 64):
+        if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+            x = x.contiguous()
+        y = torch.empty((M, w.N), dtype=torch.bfloat16, device=x.device)
+        _C.int4_gemm(y, x, w.qp, w.sp, w.zp, w.N, w.K, w.group)
+        return y
+    ws = _INT4_WORKSPACE.get(x.device)
+    if ws is None or ws.numel() < w.N * w.K:
+        raise RuntimeError(
+            "int4 workspace was not reserved for this weight "
+            f"([{w.N}, {w.K}] on {x.device})"
+        )
+    dense = int4_dequant(w, out=ws[: w.N * w.K].view(w.N, w.K))
+    return torch.nn.functional.linear(x, dense)
+
+
 def _empty_fp8_rows(shape, device):
     """Uninitialised (e4m3 `shape`, f32 [shape[0]] row scales) for an fp8
     producer to fill."""
