@@ -54,6 +54,14 @@ void greedy_sample(torch::Tensor out, torch::Tensor logits);
 void gumbel_sample(torch::Tensor out, torch::Tensor logits,
                    torch::Tensor temperature, torch::Tensor seeds,
                    int64_t step);
+void greedy_sample_logprob(torch::Tensor out, torch::Tensor out_logprob,
+                           torch::Tensor out_lse, torch::Tensor logits);
+void gumbel_sample_logprob(torch::Tensor out, torch::Tensor out_logprob,
+                           torch::Tensor out_lse, torch::Tensor logits,
+                           torch::Tensor temperature, torch::Tensor seeds,
+                           int64_t step);
+void token_logprobs(torch::Tensor out_logprob, torch::Tensor out_lse,
+                    torch::Tensor logits, torch::Tensor tokens);
 void sgmv(torch::Tensor y, torch::Tensor x, torch::Tensor A, torch::Tensor B,
           torch::Tensor idx, double scale);
 void register_chwbl(pybind11::module_& m);
@@ -74,6 +82,8 @@ void fused_add_rmsnorm_fp8(torch::Tensor out, torch::Tensor out_scale,
 void silu_and_mul_fp8(torch::Tensor out, torch::Tensor out_scale,
                       torch::Tensor x);
 void quant_fp8(torch::Tensor out, torch::Tensor out_scale, torch::Tensor x);
+void quant_fp8_div(torch::Tensor out, torch::Tensor out_scale,
+                   torch::Tensor x);
 void nucleus_stats(torch::Tensor m, torch::Tensor z, torch::Tensor logits,
                    torch::Tensor temps);
 void nucleus_accept(torch::Tensor ok, torch::Tensor logits,
@@ -137,11 +147,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("N"), pybind11::arg("M"));
   m.def("greedy_sample", &greedy_sample, "argmax sampling");
   m.def("gumbel_sample", &gumbel_sample, "temperature sampling (hash RNG)");
+  m.def("greedy_sample_logprob", &greedy_sample_logprob,
+        "argmax sampling + the token's logprob and the row logsumexp");
+  m.def("gumbel_sample_logprob", &gumbel_sample_logprob,
+        "temperature sampling + the token's logprob and the row logsumexp");
+  m.def("token_logprobs", &token_logprobs,
+        "logprob of given tokens and the row logsumexp, one launch");
   m.def("rmsnorm_fp8", &rmsnorm_fp8, "rmsnorm with fused fp8 row quant");
   m.def("fused_add_rmsnorm_fp8", &fused_add_rmsnorm_fp8,
         "residual add + rmsnorm with fused fp8 row quant");
   m.def("silu_and_mul_fp8", &silu_and_mul_fp8, "SwiGLU with fused fp8 quant");
   m.def("quant_fp8", &quant_fp8, "bf16 -> fp8 row quant");
+  m.def("quant_fp8_div", &quant_fp8_div,
+        "bf16 -> fp8 row quant, division form (Fp8Linear.forward)");
   m.def("nucleus_stats", &nucleus_stats, "per-row softmax max + Z");
   m.def("nucleus_accept", &nucleus_accept,
         "nucleus membership of sampled tokens (mass above < p, rank < k)");

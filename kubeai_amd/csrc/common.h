@@ -227,6 +227,35 @@ DEV_INLINE float row_scale_fp8(const float amax, float* smem,
   return 448.0f / gmax;
 }
 
+// Division form of the same quantization: the expression Fp8Linear.forward
+// (engine/quant.py) evaluates with torch ops on the GPU,
+//   scale = max(|x|, 1e-6) / 448;  y = clamp(x / scale, -448, 448), RNE cast.
+// x / scale and x * (448/max) round differently, so a linear whose outputs
+// are pinned to one form cannot move to the other. torch divides a GPU tensor
+// by a host scalar as a multiplication by the scalar's fp32 reciprocal; the
+// per-element x / scale is a true fp32 division.
+// Thread 0 writes *scale_out; every thread returns the scale.
+DEV_INLINE float row_scale_fp8_div(const float amax, float* smem,
+                                   float* __restrict__ scale_out) {
+  const float gmax = fmaxf(block_amax(amax, smem), 1e-6f);
+  const float scale = gmax * (float)(1.0 / 448.0);
+  if (threadIdx.x == 0) *scale_out = scale;
+  return scale;
+}
+
+// 8 floats / scale, clamped -> 8 packed e4m3 bytes
+DEV_INLINE uint2 quant8_fp8_div(const float (&f)[8], const float scale) {
+  uchar2 packed[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    packed[j].x =
+        f32_to_fp8(fminf(fmaxf(f[2 * j] / scale, -448.0f), 448.0f));
+    packed[j].y =
+        f32_to_fp8(fminf(fmaxf(f[2 * j + 1] / scale, -448.0f), 448.0f));
+  }
+  return *reinterpret_cast<uint2*>(packed);
+}
+
 // ---------------- activations ----------------
 DEV_INLINE float silu(const float x) { return x / (1.0f + __expf(-x)); }
 

@@ -3,6 +3,8 @@
 //   rmsnorm_fp8 / fused_add_rmsnorm_fp8  -> e4m3 + row scale (qkv / gate_up)
 //   silu_and_mul_fp8                     -> e4m3 + row scale (down_proj)
 //   quant_fp8                            -> e4m3 + row scale (o_proj)
+//   quant_fp8_div                        -> the same in division form
+//                                           (Fp8Linear.forward: lm_head)
 // Semantics: kubeai_amd/ops/ref.py (rmsnorm, fused_add_rmsnorm, quant_fp8).
 // The fp8 variants quantize inside the PRODUCING op, so the W8A8 path pays
 // no extra launch or HBM round trip for its dynamic activation scales.
@@ -29,16 +31,19 @@ constexpr int kBlockWide = 512;  // rows up to 32768 elems in <= 8 iterations
 constexpr int kMaxIters = 8;     // 16 iterations spill VGPRs: widen the block
 constexpr int kMaxH = kBlockWide * 8 * kMaxIters;
 
-// scale the register-held row by inv_scale and store it as e4m3 bytes
-template <int kThreads, int kIters>
+// scale the register-held row and store it as e4m3 bytes: multiplied by
+// `factor` = 448/max, or (kDiv, the division form in common.h) divided by
+// `factor` = the row scale
+template <int kThreads, int kIters, bool kDiv = false>
 DEV_INLINE void store_row_fp8(unsigned char* __restrict__ orow,
                               const float (&vals)[kIters][8],
-                              const float inv_scale, const int nvec) {
+                              const float factor, const int nvec) {
 #pragma unroll
   for (int it = 0; it < kIters; ++it) {
     const int i = threadIdx.x + it * kThreads;
     if (i < nvec)
-      *reinterpret_cast<uint2*>(orow + i * 8) = quant8_fp8(vals[it], inv_scale);
+      *reinterpret_cast<uint2*>(orow + i * 8) =
+          kDiv ? quant8_fp8_div(vals[it], factor) : quant8_fp8(vals[it], factor);
   }
 }
 
@@ -160,7 +165,7 @@ struct LoadSwiglu {  // silu(gate) * up over a packed [gate | up] row
   }
 };
 
-template <typename Producer, int kThreads, int kIters>
+template <typename Producer, bool kDiv, int kThreads, int kIters>
 __launch_bounds__(kThreads) __global__ void row_fp8_kernel(
     unsigned char* __restrict__ out,  // [T, W] fp8
     float* __restrict__ out_scale,    // [T]
@@ -182,8 +187,10 @@ __launch_bounds__(kThreads) __global__ void row_fp8_kernel(
     }
   }
   __shared__ float red[16];
-  const float inv_scale = row_scale_fp8(amax, red, out_scale + row);
-  store_row_fp8<kThreads, kIters>(out + (int64_t)row * W, vals, inv_scale, nvec);
+  const float factor = kDiv ? row_scale_fp8_div(amax, red, out_scale + row)
+                            : row_scale_fp8(amax, red, out_scale + row);
+  store_row_fp8<kThreads, kIters, kDiv>(out + (int64_t)row * W, vals, factor,
+                                        nvec);
 }
 
 // ---- host dispatch ----
@@ -245,7 +252,7 @@ void launch_rmsnorm(void* out, float* out_scale, const torch::Tensor& x,
   HIP_CHECK_KERNEL();
 }
 
-template <typename Producer>
+template <typename Producer, bool kDiv = false>
 void launch_row_fp8(torch::Tensor& out, torch::Tensor& out_scale,
                     const torch::Tensor& x) {
   const int W = x.size(-1) / Producer::kInWidth;
@@ -256,7 +263,7 @@ void launch_row_fp8(torch::Tensor& out, torch::Tensor& out_scale,
   dispatch_row<RowPolicy::kMax>(W / 8, [&](auto threads, auto iters) {
     constexpr int kThreads = decltype(threads)::value;
     constexpr int kIters = decltype(iters)::value;
-    hipLaunchKernelGGL((row_fp8_kernel<Producer, kThreads, kIters>), dim3(T),
+    hipLaunchKernelGGL((row_fp8_kernel<Producer, kDiv, kThreads, kIters>), dim3(T),
                        dim3(kThreads), 0,
                        c10::hip::getCurrentHIPStream().stream(),
                        (unsigned char*)out.data_ptr(),
@@ -302,4 +309,9 @@ void silu_and_mul_fp8(torch::Tensor out, torch::Tensor out_scale,
 
 void quant_fp8(torch::Tensor out, torch::Tensor out_scale, torch::Tensor x) {
   launch_row_fp8<LoadBf16>(out, out_scale, x);
+}
+
+void quant_fp8_div(torch::Tensor out, torch::Tensor out_scale,
+                   torch::Tensor x) {
+  launch_row_fp8<LoadBf16, true>(out, out_scale, x);
 }

@@ -14,6 +14,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from kubeai_amd import ops
+
 FP8_DTYPE = torch.float8_e4m3fn
 FP8_MAX = 448.0
 
@@ -62,9 +64,11 @@ class Fp8Linear(nn.Module):
         )
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        a_amax = x.float().abs().amax(dim=-1, keepdim=True).clamp_min(1e-6)
-        a_scale = a_amax / FP8_MAX
-        xq = (x.float() / a_scale).clamp(-FP8_MAX, FP8_MAX).to(FP8_DTYPE)
+        # scale = max(amax, 1e-6) / 448, q = e4m3(clamp(x / scale, ±448)):
+        # the division form, which rounds differently from the fused
+        # producers' x * (448 / amax). One launch for 2-D contiguous bf16 on
+        # GPU, the torch chain (byte-equal to it) for everything else.
+        xq, a_scale = ops.quant_fp8_div(x)
         if not x.is_cuda:
             return self.forward_quantized(xq, a_scale.squeeze(-1))
         return torch._scaled_mm(

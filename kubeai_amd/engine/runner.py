@@ -26,20 +26,47 @@ class _DecodeGraph:
     Replays the whole token-packed forward (norms, GEMMs, rope, cache
     write, flash-decoding attention, logits GEMM) with zero launch
     overhead; only the small input buffers are refreshed per step.
-    Sampling stays outside (its `step` scalar changes every call).
+    Sampling stays outside: the Gumbel sampler's `step` scalar changes every
+    call, and penalties, logit_bias and the choice of sampler depend on the
+    requests in the batch. It costs two launches and the step's one
+    device-to-host copy (ModelRunner.execute).
+
+    The five inputs are views of ONE int32 device buffer (the int64 slots
+    first, for alignment), mirrored by a pinned host buffer: a step pads on
+    the host and uploads once. The captured addresses never change.
+    KUBEAI_GRAPH_STAGED_INPUTS=0 uploads each input by itself from pageable
+    memory and pads with device fills instead (for A/B runs).
     """
 
+    @staticmethod
+    def _carve(buf, n: int, bt_max: int, i64):
+        """(ids, positions, slots, tables, lens) views of an int32 buffer of
+        n * (5 + bt_max) words; works on torch tensors and numpy arrays."""
+        return (
+            buf[2 * n : 3 * n],
+            buf[3 * n : 4 * n],
+            buf[: 2 * n].view(i64),
+            buf[5 * n :].reshape(n, bt_max),
+            buf[4 * n : 5 * n],
+        )
+
     def __init__(self, runner: "ModelRunner", b_pad: int, bt_max: int):
+        import numpy as np
+
         dev = runner.device
         self.b_pad = b_pad
         self.bt_max = bt_max
-        self.input_ids = torch.zeros(b_pad, dtype=torch.int32, device=dev)
-        self.positions = torch.zeros(b_pad, dtype=torch.int32, device=dev)
-        self.slots = torch.full((b_pad,), -1, dtype=torch.int64, device=dev)
-        self.block_tables = torch.zeros(
-            (b_pad, bt_max), dtype=torch.int32, device=dev
-        )
-        self.seq_lens = torch.ones(b_pad, dtype=torch.int32, device=dev)
+        self.staged = os.environ.get("KUBEAI_GRAPH_STAGED_INPUTS", "1") != "0"
+        words = b_pad * (5 + bt_max)
+        self._host = torch.zeros(words, dtype=torch.int32, pin_memory=True)
+        self._host_views = self._carve(self._host.numpy(), b_pad, bt_max, np.int64)
+        self._host_views[2][:] = -1  # slots: nothing is cached
+        self._host_views[4][:] = 1  # seq_lens
+        self._dev = self._host.to(dev)
+        (
+            self.input_ids, self.positions, self.slots, self.block_tables,
+            self.seq_lens,
+        ) = self._carve(self._dev, b_pad, bt_max, torch.int64)
         logits_idx = torch.arange(b_pad, dtype=torch.int64, device=dev)
         self.fb = ForwardBatch(
             input_ids=self.input_ids,
@@ -66,10 +93,36 @@ class _DecodeGraph:
             self.logits = runner.model.compute_logits(h[logits_idx])
 
     def run(self, input_ids, positions, slots, tables, seq_lens) -> torch.Tensor:
+        """Lists of b ints and an int32 numpy table [b, <= bt_max]. Rows past
+        b are pad rows: slot -1, seq_len 1, block 0."""
         b = len(input_ids)
-        self.input_ids[:b].copy_(input_ids, non_blocking=True)
-        self.positions[:b].copy_(positions, non_blocking=True)
-        self.slots[:b].copy_(slots, non_blocking=True)
+        if not self.staged:
+            return self._run_unstaged(input_ids, positions, slots, tables, seq_lens)
+        # The staging buffer is rewritten every step: the upload of the step
+        # before has completed, every step ends in a device-to-host copy of
+        # its samples (ModelRunner.execute).
+        h_ids, h_pos, h_slots, h_tables, h_lens = self._host_views
+        h_ids[:b], h_ids[b:] = input_ids, 0
+        h_pos[:b], h_pos[b:] = positions, 0
+        h_slots[:b], h_slots[b:] = slots, -1
+        h_lens[:b], h_lens[b:] = seq_lens, 1
+        w = tables.shape[1]
+        h_tables[:b, :w] = tables
+        h_tables[:b, w:] = 0
+        h_tables[b:] = 0
+        self._dev.copy_(self._host, non_blocking=True)
+        self.graph.replay()
+        return self.logits[:b]
+
+    def _run_unstaged(self, input_ids, positions, slots, tables, seq_lens):
+        b = len(input_ids)
+        tables = torch.from_numpy(tables)
+        i32 = lambda x: torch.tensor(x, dtype=torch.int32)
+        self.input_ids[:b].copy_(i32(input_ids), non_blocking=True)
+        self.positions[:b].copy_(i32(positions), non_blocking=True)
+        self.slots[:b].copy_(
+            torch.tensor(slots, dtype=torch.int64), non_blocking=True
+        )
         if b < self.b_pad:
             self.slots[b:].fill_(-1)
             self.seq_lens[b:].fill_(1)
@@ -77,7 +130,7 @@ class _DecodeGraph:
         self.block_tables[:b, : tables.shape[1]].copy_(tables, non_blocking=True)
         if tables.shape[1] < self.bt_max:
             self.block_tables[:b, tables.shape[1] :].fill_(0)
-        self.seq_lens[:b].copy_(seq_lens, non_blocking=True)
+        self.seq_lens[:b].copy_(i32(seq_lens), non_blocking=True)
         self.graph.replay()
         return self.logits[:b]
 
@@ -441,13 +494,7 @@ class ModelRunner:
             lens.append(t + 1)
             bt = req.block_table
             tables[i, : len(bt)] = bt
-        return g.run(
-            torch.tensor(ids, dtype=torch.int32),
-            torch.tensor(pos, dtype=torch.int32),
-            torch.tensor(slots, dtype=torch.int64),
-            torch.from_numpy(tables),
-            torch.tensor(lens, dtype=torch.int32),
-        )
+        return g.run(ids, pos, slots, tables, lens)
 
     @torch.inference_mode()
     def execute(self, out: SchedulerOutput, step: int) -> dict[str, int]:
@@ -521,9 +568,16 @@ class ModelRunner:
             logits.view(-1).scatter_add_(
                 0, flat, torch.tensor(vals, dtype=logits.dtype, device=dev_l)
             )
+        # The sampler returns the token, its logprob (logit - logsumexp(row),
+        # over the logits as they stand here: after penalties and
+        # logit_bias, untempered) and the row's lse; token and logprob reach
+        # the host in one copy, the step's only sync.
         temps = [r.params.temperature for r in sample_reqs]
+        logits = logits.contiguous()
         if all(t <= 0.0 for t in temps):
-            tokens = ops.greedy_sample(logits.contiguous())
+            res = ops.greedy_sample_logprob(logits)
+            lse = res.lse
+            tokens, logprobs = ops.sample_to_host(res)
         else:
             needs_topk = any(
                 (r.params.top_p < 1.0 or r.params.top_k > 0)
@@ -544,7 +598,7 @@ class ModelRunner:
                 # rejection nucleus sampling — no full-vocab sort; the
                 # per-row param tensors are cached across steps (the
                 # batch's sampling params rarely change step to step)
-                tokens = _sample_topk_topp(
+                tokens_t = _sample_topk_topp(
                     logits,
                     [r.params.top_p for r in sample_reqs],
                     [r.params.top_k for r in sample_reqs],
@@ -552,16 +606,30 @@ class ModelRunner:
                     t_t, seeds, step,
                     cache=self._sampling_cache,
                 ).to(dev)
+                # the token comes from the rejection loop, not from one
+                # sampler call: its logprob is a launch of its own
+                lp_t, lse = ops.token_logprobs(logits, tokens_t)
+                tokens = tokens_t.cpu().tolist()
+                logprobs = lp_t.cpu().tolist()
             else:
-                tokens = ops.gumbel_sample(logits.contiguous(), t_t, seeds, step)
-        tokens = tokens.cpu().tolist()
+                res = ops.gumbel_sample_logprob(logits, t_t, seeds, step)
+                lse = res.lse
+                tokens, logprobs = ops.sample_to_host(res)
         if any(r.params.json_mode for r in sample_reqs):
+            sampled = list(tokens)
             tokens = self._constrain_json(sample_reqs, tokens, logits)
-        tokens_t = torch.tensor(tokens, dtype=torch.int64, device=logits.device)
-        # logprob of the chosen token: logit - logsumexp(row)
-        lse = torch.logsumexp(logits, dim=-1)
-        chosen = logits.gather(1, tokens_t.view(-1, 1)).squeeze(1)
-        logprobs = (chosen - lse).cpu().tolist()
+            moved = [i for i, (a, b) in enumerate(zip(sampled, tokens)) if a != b]
+            if moved:
+                # rewritten rows only: one more launch and sync on these steps
+                lp_t, _ = ops.token_logprobs(
+                    logits[torch.tensor(moved, device=logits.device)],
+                    torch.tensor(
+                        [tokens[i] for i in moved],
+                        dtype=torch.int64, device=logits.device,
+                    ),
+                )
+                for i, lp in zip(moved, lp_t.cpu().tolist()):
+                    logprobs[i] = lp
         self.last_logprobs = {
             r.request_id: float(lp) for r, lp in zip(sample_reqs, logprobs)
         }

@@ -8,6 +8,7 @@ reference implementations (ref.py) so the engine logic is testable anywhere.
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -373,6 +374,31 @@ def quant_fp8(x):
     return out, scale
 
 
+# longest row the row kernels take (row_kernels.hip::kMaxH)
+_QUANT_DIV_MAX_H = 32768
+
+
+def quant_fp8_div(x):
+    """Row quantization in the division form Fp8Linear.forward pins
+    (ref.quant_fp8_div): (e4m3 [T, H], fp32 scales [T, 1]). One launch for a
+    2-D contiguous bf16 GPU tensor with H % 8 == 0, byte-equal to the torch
+    chain, which serves every other input."""
+    if (
+        x.is_cuda
+        and x.dtype == torch.bfloat16
+        and x.dim() == 2
+        and x.is_contiguous()
+        and x.shape[1] % 8 == 0
+        and 0 < x.shape[1] <= _QUANT_DIV_MAX_H
+        and os.environ.get("KUBEAI_QUANT_DIV_KERNEL", "1") != "0"
+    ):
+        _require_ext()
+        out, scale = _empty_fp8_rows(x.shape, x.device)
+        _C.quant_fp8_div(out, scale, x)
+        return out, scale.view(-1, 1)
+    return ref.quant_fp8_div(x)
+
+
 def greedy_sample(logits):
     if logits.is_cuda:
         _require_ext()
@@ -389,6 +415,73 @@ def gumbel_sample(logits, temperature, seeds, step: int):
         _C.gumbel_sample(out, logits, temperature, seeds, step)
         return out
     return ref.gumbel_sample(logits, temperature, seeds, step)
+
+
+class SampleResult(NamedTuple):
+    """What a *_sample_logprob op returns. On GPU the three tensors are views
+    of `packed`, one int64 [2B] buffer (B tokens, then B fp32 logprobs and B
+    fp32 lse), so a caller can bring tokens and logprobs to the host in one
+    copy: `sample_to_host`."""
+
+    tokens: torch.Tensor   # [B] int64
+    logprob: torch.Tensor  # [B] fp32: logits[b, token] - lse[b]
+    lse: torch.Tensor      # [B] fp32: logsumexp of row b
+    packed: torch.Tensor | None = None
+
+
+def _empty_sample_result(logits) -> SampleResult:
+    B = logits.shape[0]
+    packed = torch.empty(2 * B, dtype=torch.int64, device=logits.device)
+    f = packed[B:].view(torch.float32)
+    return SampleResult(packed[:B], f[:B], f[B:], packed)
+
+
+def sample_to_host(res: SampleResult) -> tuple[list[int], list[float]]:
+    """(tokens, logprobs) as Python lists: one device-to-host copy."""
+    if res.packed is None or not res.packed.is_cuda:
+        return res.tokens.tolist(), res.logprob.tolist()
+    B = res.tokens.shape[0]
+    host = res.packed[: B + (B + 1) // 2].cpu()
+    return host[:B].tolist(), host[B:].view(torch.float32)[:B].tolist()
+
+
+def greedy_sample_logprob(logits) -> SampleResult:
+    """greedy_sample's token, plus its log-probability and the row's
+    logsumexp. On GPU the sampler's own two launches produce all three."""
+    if logits.is_cuda:
+        _require_ext()
+        res = _empty_sample_result(logits)
+        _C.greedy_sample_logprob(res.tokens, res.logprob, res.lse, logits)
+        return res
+    return SampleResult(*ref.greedy_sample_logprob(logits))
+
+
+def gumbel_sample_logprob(logits, temperature, seeds, step: int) -> SampleResult:
+    """gumbel_sample's token, plus its log-probability and the row's
+    logsumexp, both over `logits` as passed (untempered, no noise)."""
+    if logits.is_cuda:
+        _require_ext()
+        res = _empty_sample_result(logits)
+        _C.gumbel_sample_logprob(
+            res.tokens, res.logprob, res.lse, logits, temperature, seeds, step
+        )
+        return res
+    return SampleResult(
+        *ref.gumbel_sample_logprob(logits, temperature, seeds, step)
+    )
+
+
+def token_logprobs(logits, tokens):
+    """(logprob [B], lse [B]) of int64 tokens[b] in row b of fp32 logits, for
+    tokens that do not come from a *_sample_logprob op. One launch on GPU;
+    lse is bit-identical to the one those ops return."""
+    if logits.is_cuda:
+        _require_ext()
+        B = logits.shape[0]
+        out = torch.empty((2, B), dtype=torch.float32, device=logits.device)
+        _C.token_logprobs(out[0], out[1], logits, tokens)
+        return out[0], out[1]
+    return ref.token_logprobs(logits, tokens)
 
 
 def nucleus_stats(logits, temps):

@@ -338,6 +338,30 @@ def gumbel_sample(
     return out
 
 
+def token_logprobs(
+    logits: torch.Tensor,  # [B, V]
+    tokens: torch.Tensor,  # [B] int64
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """(logprob of tokens[b] in row b, logsumexp of row b): the torch
+    expressions the runner used before the sampler returned them."""
+    lse = torch.logsumexp(logits, dim=-1)
+    chosen = logits.gather(1, tokens.view(-1, 1)).squeeze(1)
+    return chosen - lse, lse
+
+
+def greedy_sample_logprob(logits: torch.Tensor):
+    """(token, its logprob, row logsumexp)."""
+    tokens = greedy_sample(logits)
+    return (tokens, *token_logprobs(logits, tokens))
+
+
+def gumbel_sample_logprob(logits, temperature, seeds, step: int):
+    """(token, its logprob, row logsumexp). The logprob is over `logits` as
+    passed: untempered, without the Gumbel noise."""
+    tokens = gumbel_sample(logits, temperature, seeds, step)
+    return (tokens, *token_logprobs(logits, tokens))
+
+
 def topk_topp_sample(
     logits: torch.Tensor,  # [B, V]
     temperature: torch.Tensor,  # [B]
@@ -379,4 +403,14 @@ def quant_fp8(x: torch.Tensor):
     amax = xf.abs().amax(dim=-1).clamp_min(1e-6)
     scale = amax / 448.0
     q = (xf / scale[:, None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+    return q, scale
+
+
+def quant_fp8_div(x: torch.Tensor):
+    """The quantization Fp8Linear.forward pins, as torch evaluates it on the
+    device of `x` (csrc/common.h::row_scale_fp8_div is its GPU kernel form).
+    Returns (e4m3 like x, fp32 scales [..., 1])."""
+    amax = x.float().abs().amax(dim=-1, keepdim=True).clamp_min(1e-6)
+    scale = amax / 448.0
+    q = (x.float() / scale).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
     return q, scale
