@@ -28,7 +28,9 @@
 
 namespace {
 
-constexpr int kWaves = 2;  // 2 waves/workgroup: fits double-buffered tiles
+// 2 waves/workgroup, one LDS tile buffer each: 21.5 KB at G = 4, hd 128,
+// bf16, which lets 6 workgroups share a CU (profiles/r09_decode_step.md)
+constexpr int kWaves = 2;
 constexpr int kBlockThreads = kWaves * WAVE_SIZE;
 constexpr int kBS = 16;   // cache block size (tokens)
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;  // v_dot2 operand
@@ -112,7 +114,10 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
   const int blk_lo = blk_base + split * chunk;
   const int blk_hi = min(n_blocks, blk_lo + chunk);
 
-  // LDS: per-wave double-buffered KV tiles + merge scratch. Element type
+  // LDS: one KV tile buffer per wave + merge scratch. The wave that reads a
+  // tile is the wave that overwrites it with the next one, after the compute,
+  // in program order (LDS operations of one wave complete in order), so a
+  // second buffer would buy nothing and cost occupancy. Element type
   // follows the cache: bf16 stages bf16; fp8 stages the RAW e5m2 bytes
   // (half the LDS footprint/traffic) and converts during compute with the
   // native packed bf8->f32 instruction (v_cvt_pk_f32_bf8). 8-element row
@@ -121,8 +126,8 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
   constexpr int PARTS = HD / 32;    // lanes per token in scoring
   constexpr int TOKP = 64 / PARTS;  // tokens scored per pass
   constexpr int EPL = HD / 64;      // output elems owned per lane
-  __shared__ CT k_lds[kWaves][2][kBS][HD + kPad];
-  __shared__ CT v_lds[kWaves][2][kBS][HD + kPad];
+  __shared__ CT k_lds[kWaves][kBS][HD + kPad];
+  __shared__ CT v_lds[kWaves][kBS][HD + kPad];
   __shared__ float merge_o[kWaves][G][HD];
   __shared__ float merge_ml[kWaves][G][2];
 
@@ -220,12 +225,19 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
 
   // T14 async-stage: global loads for block n+1 issue before block n's
   // compute (their latency hides under it); the register payload lands in
-  // the other LDS buffer just before it is needed. Per-wave buffers ->
-  // no barriers anywhere in the loop.
+  // the wave's LDS buffer once block n's compute has read it. Per-wave
+  // buffers -> no barriers anywhere in the loop.
   // staging vector = 8 elements: 16 B (bf16) or 8 B (raw fp8 bytes)
   using StageVec = std::conditional_t<sizeof(CT) == 2, ushort8, uint64_t>;
   constexpr int NS = (kBS * HD / 8) / WAVE_SIZE;
   StageVec stage_k[NS], stage_v[NS];  // this lane's vectors of each tile
+  // The type LDS is written through. A tile is stored as staging vectors and
+  // read back as 4- and 2-byte words; the fp8 vector is a plain uint64_t,
+  // which type-based alias analysis takes to be unrelated to those reads.
+  // With the one buffer at a fixed address the compiler then moved the first
+  // tile's reads above its stores. may_alias keeps program order (the bf16
+  // vector type aliases everything already).
+  typedef StageVec __attribute__((may_alias)) LdsVec;
 
   auto issue_tile = [&](const int64_t blk) {
     const CT* base_k = k_cache + ((blk * n_kv + kh) * kBS) * HD;
@@ -239,20 +251,17 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
     }
   };
   auto issue_loads = [&](int blk_i) { issue_tile(bt[blk_i]); };
-  auto write_tile = [&](int buf) {
+  auto write_tile = [&]() {
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       const int vec = lane + i * WAVE_SIZE;  // 8-element vector index
       const int row = vec / (HD / 8);
       const int col = vec % (HD / 8);
-      *reinterpret_cast<StageVec*>(&k_lds[wave][buf][row][col * 8]) =
-          stage_k[i];
-      *reinterpret_cast<StageVec*>(&v_lds[wave][buf][row][col * 8]) =
-          stage_v[i];
+      *reinterpret_cast<LdsVec*>(&k_lds[wave][row][col * 8]) = stage_k[i];
+      *reinterpret_cast<LdsVec*>(&v_lds[wave][row][col * 8]) = stage_v[i];
     }
   };
 
-  int cur = 0;
   if (first < blk_hi) {
     if constexpr (RAW)
       issue_tile(blk_first);
@@ -342,7 +351,7 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
       }
     }
   }
-  if (first < blk_hi) write_tile(0);
+  if (first < blk_hi) write_tile();
 
   for (int blk_i = first; blk_i < blk_hi; blk_i += kWaves) {
     const int tile_start = blk_i * kBS;
@@ -354,9 +363,9 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
       // that row: put the bytes just stored over it (same wave as the
       // write_tile before, program order — no barrier)
       if (blk_i == row_blk && lane < 2 * RV) {
-        CT* dst = lane < RV ? &k_lds[wave][cur][(L - 1) % kBS][lane * 8]
-                            : &v_lds[wave][cur][(L - 1) % kBS][(lane - RV) * 8];
-        *reinterpret_cast<StageVec*>(dst) = row_vec;
+        CT* dst = lane < RV ? &k_lds[wave][(L - 1) % kBS][lane * 8]
+                            : &v_lds[wave][(L - 1) % kBS][(lane - RV) * 8];
+        *reinterpret_cast<LdsVec*>(dst) = row_vec;
       }
     }
 
@@ -374,7 +383,7 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
         // (replaces 2 unpacks + 2 fma per (g, j) — a 3x VALU cut in the
         // score phase)
         const uint32_t* krow = reinterpret_cast<const uint32_t*>(
-            &k_lds[wave][cur][tok][part * 32]);
+            &k_lds[wave][tok][part * 32]);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
           const bf16x2v kk = __builtin_bit_cast(bf16x2v, krow[j]);
@@ -387,7 +396,7 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
         // raw e5m2 slice: each uint32 holds 4 bytes -> 4 elements; the
         // packed bf8->f32 convert does 2 per instruction
         const uint32_t* krow = reinterpret_cast<const uint32_t*>(
-            &k_lds[wave][cur][tok][part * 32]);
+            &k_lds[wave][tok][part * 32]);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const uint32_t kk = krow[j];
@@ -447,7 +456,7 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
 #pragma unroll
           for (int e = 0; e < EPL; e += 2) {
             const uint32_t vr = *reinterpret_cast<const uint32_t*>(
-                &v_lds[wave][cur][t][EPL * lane + e]);
+                &v_lds[wave][t][EPL * lane + e]);
             vv[e] = bf16_to_f32((ushort)(vr & 0xffff));
             vv[e + 1] = bf16_to_f32((ushort)(vr >> 16));
           }
@@ -455,7 +464,7 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
 #pragma unroll
           for (int e = 0; e < EPL; e += 2) {
             const uint32_t vr = *reinterpret_cast<const ushort*>(
-                &v_lds[wave][cur][t][EPL * lane + e]);
+                &v_lds[wave][t][EPL * lane + e]);
             const floatx2 vf = __builtin_amdgcn_cvt_pk_f32_bf8(vr, false);
             vv[e] = vf.x;
             vv[e + 1] = vf.y;
@@ -471,9 +480,9 @@ __launch_bounds__(kBlockThreads) __global__ void paged_decode_kernel(
       }
     }
 
-    // land the prefetched tile in the other buffer (waits only on vmcnt)
-    if (blk_i + kWaves < blk_hi) write_tile(cur ^ 1);
-    cur ^= 1;
+    // land the prefetched tile over the one just consumed (waits only on
+    // vmcnt; the reads above are earlier LDS operations of the same wave)
+    if (blk_i + kWaves < blk_hi) write_tile();
   }
 
   // cross-wave merge through LDS

@@ -79,6 +79,13 @@ void rmsnorm_fp8(torch::Tensor out, torch::Tensor out_scale, torch::Tensor x,
 void fused_add_rmsnorm_fp8(torch::Tensor out, torch::Tensor out_scale,
                            torch::Tensor x, torch::Tensor residual,
                            torch::Tensor weight, double eps);
+void fused_add_rmsnorm_fp8_div(torch::Tensor out, torch::Tensor out_scale,
+                               torch::Tensor x, torch::Tensor residual,
+                               torch::Tensor weight, double eps,
+                               bool write_rows);
+void embed_rmsnorm_fp8(torch::Tensor out, torch::Tensor out_scale,
+                       torch::Tensor x_out, torch::Tensor ids,
+                       torch::Tensor table, torch::Tensor weight, double eps);
 void silu_and_mul_fp8(torch::Tensor out, torch::Tensor out_scale,
                       torch::Tensor x);
 void quant_fp8(torch::Tensor out, torch::Tensor out_scale, torch::Tensor x);
@@ -156,6 +163,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fp8", &rmsnorm_fp8, "rmsnorm with fused fp8 row quant");
   m.def("fused_add_rmsnorm_fp8", &fused_add_rmsnorm_fp8,
         "residual add + rmsnorm with fused fp8 row quant");
+  m.def("fused_add_rmsnorm_fp8_div", &fused_add_rmsnorm_fp8_div,
+        "residual add + rmsnorm, then the division-form fp8 row quant of its "
+        "bf16 row (lm_head's input)");
+  m.def("embed_rmsnorm_fp8", &embed_rmsnorm_fp8,
+        "embedding gather + rmsnorm with fused fp8 row quant (layer 0)");
   m.def("silu_and_mul_fp8", &silu_and_mul_fp8, "SwiGLU with fused fp8 quant");
   m.def("quant_fp8", &quant_fp8, "bf16 -> fp8 row quant");
   m.def("quant_fp8_div", &quant_fp8_div,

@@ -5,6 +5,10 @@
 //   quant_fp8                            -> e4m3 + row scale (o_proj)
 //   quant_fp8_div                        -> the same in division form
 //                                           (Fp8Linear.forward: lm_head)
+//   embed_rmsnorm_fp8                    -> rmsnorm_fp8 of gathered embedding
+//                                           rows, which it also writes out
+//   fused_add_rmsnorm_fp8_div            -> quant_fp8_div of the bf16 row that
+//                                           fused_add_rmsnorm would write
 // Semantics: kubeai_amd/ops/ref.py (rmsnorm, fused_add_rmsnorm, quant_fp8).
 // The fp8 variants quantize inside the PRODUCING op, so the W8A8 path pays
 // no extra launch or HBM round trip for its dynamic activation scales.
@@ -52,19 +56,36 @@ DEV_INLINE void store_row_fp8(unsigned char* __restrict__ orow,
 // thread sums the same squares in the same order as a strided runtime loop
 // would. Rows beyond 16384 elements (no model preset has one) use the
 // 512-thread block, which changes the sum order.
-template <bool kFused, bool kFp8Out, int kThreads, int kIters>
+//
+// kEmbed (not fused, fp8 out): x is an embedding table [V, H] and row t reads
+// table row ids[t], clamped into [0, V); the row is also written to
+// `residual`, which here is a plain output (layer 0's residual stream).
+// kDiv (fused, fp8 out): the fp8 epilogue is the division form, applied to
+// the bf16-ROUNDED normalized row, so bytes and scales equal quant_fp8_div
+// run on fused_add_rmsnorm's output. `write_rows` says whether x and
+// residual are updated as fused_add_rmsnorm updates them, or left alone.
+template <bool kFused, bool kFp8Out, int kThreads, int kIters,
+          bool kDiv = false, bool kEmbed = false>
 __launch_bounds__(kThreads) __global__ void rmsnorm_kernel(
     // [T, H] e4m3 or bf16 (== x for fused bf16)
     std::conditional_t<kFp8Out, unsigned char, ushort>* __restrict__ out,
     float* __restrict__ out_scale,  // [T] (fp8 out only)
-    ushort* __restrict__ x,         // [T, H] bf16
-    ushort* __restrict__ residual,  // [T, H] bf16 (fused only; updated)
+    ushort* __restrict__ x,         // [T, H] bf16 (kEmbed: [V, H], read only)
+    ushort* __restrict__ residual,  // [T, H] bf16 (fused: updated; kEmbed: out)
     const ushort* __restrict__ w,   // [H] bf16
-    const float eps, const int H) {
+    const float eps, const int H,
+    const int32_t* __restrict__ ids = nullptr,  // [T] (kEmbed only)
+    const int V = 0,                            // kEmbed only
+    const bool write_rows = true) {             // kDiv only
+  static_assert(!kEmbed || (kFp8Out && !kFused && !kDiv));
+  static_assert(!kDiv || (kFp8Out && kFused));
   const int row = blockIdx.x;
-  ushort8* xrow = reinterpret_cast<ushort8*>(x + (int64_t)row * H);
-  ushort8* rrow =
-      kFused ? reinterpret_cast<ushort8*>(residual + (int64_t)row * H) : nullptr;
+  int64_t src = row;
+  if constexpr (kEmbed) src = min(max(ids[row], 0), V - 1);
+  ushort8* xrow = reinterpret_cast<ushort8*>(x + src * H);
+  ushort8* rrow = (kFused || kEmbed)
+                      ? reinterpret_cast<ushort8*>(residual + (int64_t)row * H)
+                      : nullptr;
   const ushort8* wv = reinterpret_cast<const ushort8*>(w);
   const int nvec = H / 8;
 
@@ -86,11 +107,14 @@ __launch_bounds__(kThreads) __global__ void rmsnorm_kernel(
       }
       if constexpr (kFused) {
         // write residual' = x + residual back
-        ushort8 rv;
+        if (!kDiv || write_rows) {
+          ushort8 rv;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) rv[j] = f32_to_bf16(vals[it][j]);
-        rrow[i] = rv;
+          for (int j = 0; j < 8; ++j) rv[j] = f32_to_bf16(vals[it][j]);
+          rrow[i] = rv;
+        }
       }
+      if constexpr (kEmbed) rrow[i] = xv;
     }
   }
   // the norm weights do not depend on the reduction: load them above it
@@ -105,7 +129,30 @@ __launch_bounds__(kThreads) __global__ void rmsnorm_kernel(
   const float total = block_reduce_sum(ssum, red);
   const float inv_rms = rsqrtf(total / (float)H + eps);
 
-  if constexpr (kFp8Out) {
+  if constexpr (kDiv) {
+    // the bf16 row of the plain fused kernel, kept in registers as the
+    // values quant_fp8_div would read back
+    float amax = 0.f;
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int i = threadIdx.x + it * kThreads;
+      if (i < nvec) {
+        ushort8 ov;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          // (v * inv_rms) * w: association pinned for bit-compatibility
+          ov[j] = f32_to_bf16(vals[it][j] * inv_rms * bf16_to_f32(wreg[it][j]));
+          vals[it][j] = bf16_to_f32(ov[j]);
+          amax = fmaxf(amax, fabsf(vals[it][j]));
+        }
+        if (write_rows) xrow[i] = ov;
+      }
+    }
+    __syncthreads();  // red[] reuse
+    const float scale = row_scale_fp8_div(amax, red, out_scale + row);
+    store_row_fp8<kThreads, kIters, true>(out + (int64_t)row * H, vals, scale,
+                                          nvec);
+  } else if constexpr (kFp8Out) {
     // normalize in registers, track amax
     float amax = 0.f;
 #pragma unroll
@@ -233,21 +280,31 @@ void check_row_op(const torch::Tensor& x, const int64_t W) {
   TORCH_CHECK(W % 8 == 0 && W <= kMaxH);
 }
 
-template <bool kFused, bool kFp8Out>
+// x is the [T, H] input, or (ids set) the [V, H] table its rows come from
+template <bool kFused, bool kFp8Out, bool kDiv = false, bool kEmbed = false>
 void launch_rmsnorm(void* out, float* out_scale, const torch::Tensor& x,
-                    void* residual, const torch::Tensor& weight, double eps) {
+                    void* residual, const torch::Tensor& weight, double eps,
+                    const torch::Tensor* ids = nullptr,
+                    const bool write_rows = true) {
   const int H = x.size(-1);
   check_row_op(x, H);
-  const int T = x.numel() / H;
+  const int T = kEmbed ? ids->numel() : x.numel() / H;
+  if constexpr (kDiv || kEmbed) {
+    TORCH_CHECK(weight.is_contiguous() && weight.numel() == H &&
+                weight.scalar_type() == torch::kBFloat16);
+    if (T == 0) return;
+  }
   using out_t = std::conditional_t<kFp8Out, unsigned char, ushort>;
   dispatch_row<RowPolicy::kNorm>(H / 8, [&](auto threads, auto iters) {
     constexpr int kThreads = decltype(threads)::value;
     constexpr int kIters = decltype(iters)::value;
-    hipLaunchKernelGGL((rmsnorm_kernel<kFused, kFp8Out, kThreads, kIters>),
-                       dim3(T), dim3(kThreads), 0,
-                       c10::hip::getCurrentHIPStream().stream(), (out_t*)out,
-                       out_scale, (ushort*)x.data_ptr(), (ushort*)residual,
-                       (const ushort*)weight.data_ptr(), (float)eps, H);
+    hipLaunchKernelGGL(
+        (rmsnorm_kernel<kFused, kFp8Out, kThreads, kIters, kDiv, kEmbed>),
+        dim3(T), dim3(kThreads), 0, c10::hip::getCurrentHIPStream().stream(),
+        (out_t*)out, out_scale, (ushort*)x.data_ptr(), (ushort*)residual,
+        (const ushort*)weight.data_ptr(), (float)eps, H,
+        kEmbed ? ids->data_ptr<int32_t>() : nullptr,
+        kEmbed ? (int)x.size(0) : 0, write_rows);
   });
   HIP_CHECK_KERNEL();
 }
@@ -300,6 +357,46 @@ void fused_add_rmsnorm_fp8(torch::Tensor out, torch::Tensor out_scale,
   TORCH_CHECK(residual.is_contiguous());
   launch_rmsnorm<true, true>(out.data_ptr(), out_scale.data_ptr<float>(), x,
                              residual.data_ptr(), weight, eps);
+}
+
+// (out, out_scale) = quant_fp8_div of the row fused_add_rmsnorm would leave
+// in x. write_rows: also update x and residual as fused_add_rmsnorm does;
+// otherwise both are only read.
+void fused_add_rmsnorm_fp8_div(torch::Tensor out, torch::Tensor out_scale,
+                               torch::Tensor x, torch::Tensor residual,
+                               torch::Tensor weight, double eps,
+                               bool write_rows) {
+  TORCH_CHECK(residual.is_contiguous() && residual.sizes() == x.sizes() &&
+              residual.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(out.is_contiguous() && out.numel() == x.numel() &&
+              out.element_size() == 1);
+  TORCH_CHECK(out_scale.is_contiguous() &&
+              out_scale.scalar_type() == torch::kFloat32 &&
+              out_scale.numel() * x.size(-1) == x.numel());
+  launch_rmsnorm<true, true, true>(out.data_ptr(), out_scale.data_ptr<float>(),
+                                   x, residual.data_ptr(), weight, eps, nullptr,
+                                   write_rows);
+}
+
+// x_out[t] = table[ids[t]] (ids clamped into the table), and (out, out_scale)
+// = rmsnorm_fp8 of that row.
+void embed_rmsnorm_fp8(torch::Tensor out, torch::Tensor out_scale,
+                       torch::Tensor x_out, torch::Tensor ids,
+                       torch::Tensor table, torch::Tensor weight, double eps) {
+  TORCH_CHECK(table.dim() == 2 && table.size(0) >= 1);
+  TORCH_CHECK(ids.dim() == 1 && ids.is_contiguous() &&
+              ids.scalar_type() == torch::kInt32);
+  const int64_t T = ids.numel(), H = table.size(1);
+  TORCH_CHECK(x_out.is_contiguous() && x_out.dim() == 2 && x_out.size(0) == T &&
+              x_out.size(1) == H && x_out.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(out.is_contiguous() && out.numel() == T * H &&
+              out.element_size() == 1);
+  TORCH_CHECK(out_scale.is_contiguous() &&
+              out_scale.scalar_type() == torch::kFloat32 &&
+              out_scale.numel() == T);
+  launch_rmsnorm<false, true, false, true>(
+      out.data_ptr(), out_scale.data_ptr<float>(), table, x_out.data_ptr(),
+      weight, eps, &ids);
 }
 
 void silu_and_mul_fp8(torch::Tensor out, torch::Tensor out_scale,

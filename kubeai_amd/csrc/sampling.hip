@@ -23,7 +23,15 @@
 // No atomics and one fixed order, so results are bit-identical from run to
 // run, and between the two-stage sampler and token_logprobs, which walks the
 // same chunks with the same thread mapping inside one workgroup.
+//
+// Logits are fp32 or bf16 (the lm_head GEMM's own output type). A bf16 logit
+// widens to fp32 exactly, and all arithmetic is on the widened value, so
+// token, logprob and lse are bit-identical to a run on logits.float(). Loads
+// are one element per lane: no row alignment is assumed (a bf16 row of odd V
+// starts 2 B aligned).
 #include <torch/extension.h>
+
+#include <type_traits>
 
 #include "common.h"
 #include "dispatch.h"
@@ -37,6 +45,10 @@ constexpr int kSplits = 32;
 // registers between the max sweep and the expf sweep; a longer one is read
 // again (from L2)
 constexpr int kRegIters = 16;
+
+// LT = logits element: float, or ushort holding bf16 bits
+DEV_INLINE float logit_f32(const float x) { return x; }
+DEV_INLINE float logit_f32(const ushort x) { return bf16_to_f32(x); }
 
 DEV_INLINE float max_waves(const float (&s)[kWaves]) {
   return fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
@@ -69,10 +81,10 @@ struct SamplePartials {  // each [B, kSplits]
   float* s;              // kLse: sum of expf(x - m)
 };
 
-template <bool kGumbel, bool kLse, bool kRegs>
+template <typename LT, bool kGumbel, bool kLse, bool kRegs>
 __launch_bounds__(kBlock) __global__ void sample_stage1(
     const SamplePartials part,
-    const float* __restrict__ logits,      // [B, V]
+    const LT* __restrict__ logits,          // [B, V]
     const float* __restrict__ temperature,  // [B]
     const int64_t* __restrict__ seeds,      // [B]
     const int64_t step, const int V) {
@@ -82,7 +94,7 @@ __launch_bounds__(kBlock) __global__ void sample_stage1(
   const int chunk = (V + kSplits - 1) / kSplits;
   const int lo = split * chunk;
   const int hi = min(V, lo + chunk);
-  const float* row = logits + (int64_t)b * V;
+  const LT* row = logits + (int64_t)b * V;
   float temp = 1.0f;
   uint64_t key = 0;
   bool greedy = !kGumbel;
@@ -110,10 +122,27 @@ __launch_bounds__(kBlock) __global__ void sample_stage1(
   float x[kRegs ? kRegIters : 1];
   if constexpr (kRegs) {
     // all loads first, then the sweep: x[] is indexed by constants only
+    if constexpr (std::is_same_v<LT, float>) {
 #pragma unroll
-    for (int it = 0; it < kRegIters; ++it) {
-      const int v = lo + threadIdx.x + it * kBlock;
-      x[it] = v < hi ? row[v] : -INFINITY;
+      for (int it = 0; it < kRegIters; ++it) {
+        const int v = lo + threadIdx.x + it * kBlock;
+        x[it] = v < hi ? row[v] : -INFINITY;
+      }
+    } else {
+      // bf16: behind the `v < hi` guard the compiler widened each element
+      // next to its load and waited on the 16 loads one by one (13.5 us
+      // against 8.8 us for fp32 at 40 x 128256,
+      // profiles/r09_decode_step.md). Unguarded loads at an index clamped
+      // into the row go out together; the guard moves to the widening.
+      uint32_t raw[kRegIters];
+#pragma unroll
+      for (int it = 0; it < kRegIters; ++it)
+        raw[it] = row[min(lo + (int)threadIdx.x + it * kBlock, V - 1)];
+#pragma unroll
+      for (int it = 0; it < kRegIters; ++it) {
+        const int v = lo + threadIdx.x + it * kBlock;
+        x[it] = v < hi ? logit_f32((ushort)raw[it]) : -INFINITY;
+      }
     }
 #pragma unroll
     for (int it = 0; it < kRegIters; ++it) {
@@ -121,7 +150,8 @@ __launch_bounds__(kBlock) __global__ void sample_stage1(
       if (v < hi) visit(v, x[it]);
     }
   } else {
-    for (int v = lo + threadIdx.x; v < hi; v += kBlock) visit(v, row[v]);
+    for (int v = lo + threadIdx.x; v < hi; v += kBlock)
+      visit(v, logit_f32(row[v]));
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -167,7 +197,7 @@ __launch_bounds__(kBlock) __global__ void sample_stage1(
       }
     } else {
       for (int v = lo + threadIdx.x; v < hi; v += kBlock)
-        s += expf(row[v] - ref);
+        s += expf(logit_f32(row[v]) - ref);
     }
     s = wave_reduce_sum(s);
     if (threadIdx.x % WAVE_SIZE == 0) ssum[wave] = s;
@@ -179,12 +209,12 @@ __launch_bounds__(kBlock) __global__ void sample_stage1(
   }
 }
 
-template <bool kLse>
+template <typename LT, bool kLse>
 __global__ void sample_stage2(int64_t* __restrict__ out,
                               float* __restrict__ out_logprob,  // kLse
                               float* __restrict__ out_lse,      // kLse
                               const SamplePartials part,
-                              const float* __restrict__ logits,  // kLse
+                              const LT* __restrict__ logits,  // kLse
                               const int V) {
   const int b = blockIdx.x;
   const int lane = threadIdx.x;
@@ -206,7 +236,7 @@ __global__ void sample_stage2(int64_t* __restrict__ out,
     if (lane == 0) {
       // a row of NaNs has no argmax (index V, as greedy_sample reports it)
       const float xt =
-          best_idx < V ? logits[(int64_t)b * V + best_idx] : (float)NAN;
+          best_idx < V ? logit_f32(logits[(int64_t)b * V + best_idx]) : (float)NAN;
       out_logprob[b] = xt - lse;
       out_lse[b] = lse;
     }
@@ -220,17 +250,18 @@ __global__ void sample_stage2(int64_t* __restrict__ out,
 constexpr int kGroups = 4;
 static_assert(kSplits % kGroups == 0, "every group runs every round");
 
+template <typename LT>
 __launch_bounds__(kBlock* kGroups) __global__ void token_logprobs_kernel(
     float* __restrict__ out_logprob,    // [B]
     float* __restrict__ out_lse,        // [B]
-    const float* __restrict__ logits,   // [B, V]
+    const LT* __restrict__ logits,      // [B, V]
     const int64_t* __restrict__ tokens,  // [B]
     const int V) {
   const int b = blockIdx.x;
   const int g = threadIdx.x / kBlock;
   const int tid = threadIdx.x % kBlock;
   const int wave = tid / WAVE_SIZE;
-  const float* row = logits + (int64_t)b * V;
+  const LT* row = logits + (int64_t)b * V;
   const int chunk = (V + kSplits - 1) / kSplits;
   __shared__ float smax[kGroups][kWaves];
   __shared__ float ssum[kGroups][kWaves];
@@ -241,14 +272,16 @@ __launch_bounds__(kBlock* kGroups) __global__ void token_logprobs_kernel(
     const int lo = split * chunk;
     const int hi = min(V, lo + chunk);
     float m = -INFINITY;
-    for (int v = lo + tid; v < hi; v += kBlock) m = fmaxf(m, row[v]);
+    for (int v = lo + tid; v < hi; v += kBlock)
+      m = fmaxf(m, logit_f32(row[v]));
     m = wave_reduce_max(m);
     if (tid % WAVE_SIZE == 0) smax[g][wave] = m;
     __syncthreads();
     m = max_waves(smax[g]);
     const float ref = exp_ref(m);
     float s = 0.f;
-    for (int v = lo + tid; v < hi; v += kBlock) s += expf(row[v] - ref);
+    for (int v = lo + tid; v < hi; v += kBlock)
+      s += expf(logit_f32(row[v]) - ref);
     s = wave_reduce_sum(s);
     if (tid % WAVE_SIZE == 0) ssum[g][wave] = s;
     __syncthreads();
@@ -264,7 +297,7 @@ __launch_bounds__(kBlock* kGroups) __global__ void token_logprobs_kernel(
                                 (lane < kSplits) ? ps[lane] : 0.f);
     if (lane == 0) {
       const int64_t t = tokens[b];
-      const float xt = (t >= 0 && t < V) ? row[t] : (float)NAN;
+      const float xt = (t >= 0 && t < V) ? logit_f32(row[t]) : (float)NAN;
       out_logprob[b] = xt - lse;
       out_lse[b] = lse;
     }
@@ -273,8 +306,18 @@ __launch_bounds__(kBlock* kGroups) __global__ void token_logprobs_kernel(
 
 void check_logits(const torch::Tensor& logits) {
   TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous());
-  TORCH_CHECK(logits.scalar_type() == torch::kFloat32,
-              "sampling expects fp32 logits");
+  TORCH_CHECK(logits.scalar_type() == torch::kFloat32 ||
+                  logits.scalar_type() == torch::kBFloat16,
+              "sampling expects fp32 or bf16 logits");
+}
+
+// calls f with a null pointer of the kernels' element type for `logits`
+template <typename F>
+void dispatch_logits(const torch::Tensor& logits, F&& f) {
+  if (logits.scalar_type() == torch::kBFloat16)
+    f(static_cast<const ushort*>(nullptr));
+  else
+    f(static_cast<const float*>(nullptr));
 }
 
 // [B] outputs of the dtype T on the device of `logits`
@@ -302,17 +345,20 @@ void launch_sample(int64_t* out, float* out_logprob, float* out_lse,
                             kLse ? reinterpret_cast<float*>(w + 3 * n) : nullptr};
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const int chunk = (V + kSplits - 1) / kSplits;
-  dispatch_bool(kLse && chunk <= kBlock * kRegIters, [&](auto regs) {
-    constexpr bool kRegs = kLse && decltype(regs)::value;
-    hipLaunchKernelGGL((sample_stage1<kGumbel, kLse, kRegs>),
-                       dim3(B, kSplits), dim3(kBlock), 0, stream, part,
-                       logits.data_ptr<float>(), temp_ptr, seed_ptr, step, V);
+  dispatch_logits(logits, [&](auto null_lt) {
+    using LT = std::remove_const_t<std::remove_pointer_t<decltype(null_lt)>>;
+    const LT* lp = static_cast<const LT*>(logits.data_ptr());
+    dispatch_bool(kLse && chunk <= kBlock * kRegIters, [&](auto regs) {
+      constexpr bool kRegs = kLse && decltype(regs)::value;
+      hipLaunchKernelGGL((sample_stage1<LT, kGumbel, kLse, kRegs>),
+                         dim3(B, kSplits), dim3(kBlock), 0, stream, part, lp,
+                         temp_ptr, seed_ptr, step, V);
+    });
+    HIP_CHECK_KERNEL();
+    hipLaunchKernelGGL((sample_stage2<LT, kLse>), dim3(B), dim3(WAVE_SIZE), 0,
+                       stream, out, out_logprob, out_lse, part, lp, V);
+    HIP_CHECK_KERNEL();
   });
-  HIP_CHECK_KERNEL();
-  hipLaunchKernelGGL(sample_stage2<kLse>, dim3(B), dim3(WAVE_SIZE), 0, stream,
-                     out, out_logprob, out_lse, part, logits.data_ptr<float>(),
-                     V);
-  HIP_CHECK_KERNEL();
 }
 
 void check_gumbel(const torch::Tensor& logits, const torch::Tensor& temperature,
@@ -373,9 +419,13 @@ void token_logprobs(torch::Tensor out_logprob, torch::Tensor out_lse,
   float* lse = row_output<float>(out_lse, logits);
   const int64_t* tok = row_output<int64_t>(tokens, logits);
   if (B == 0) return;
-  hipLaunchKernelGGL(token_logprobs_kernel, dim3(B), dim3(kBlock * kGroups), 0,
-                     c10::hip::getCurrentHIPStream().stream(), lp, lse,
-                     logits.data_ptr<float>(), tok, V);
+  dispatch_logits(logits, [&](auto null_lt) {
+    using LT = std::remove_const_t<std::remove_pointer_t<decltype(null_lt)>>;
+    hipLaunchKernelGGL(token_logprobs_kernel<LT>, dim3(B),
+                       dim3(kBlock * kGroups), 0,
+                       c10::hip::getCurrentHIPStream().stream(), lp, lse,
+                       static_cast<const LT*>(logits.data_ptr()), tok, V);
+  });
   HIP_CHECK_KERNEL();
 }
 

@@ -81,16 +81,27 @@ class _DecodeGraph:
             prefill_block_tables=None,
             logits_indices=logits_idx,
         )
+        # Every row of a decode step is sampled, so a model that has
+        # forward_logits runs the head on the hidden rows as they are (final
+        # norm fused with lm_head's input quantization, no row gather) and
+        # leaves the logits in bf16: ModelRunner.execute widens them on the
+        # steps that edit logits, the samplers read bf16.
+        fused_head = getattr(runner.model, "forward_logits", None)
+
+        def step_logits():
+            if fused_head is not None:
+                return fused_head(self.fb, fp32=False)
+            h = runner.model(self.fb)
+            return runner.model.compute_logits(h[logits_idx])
+
         # warmup outside capture (allocator, hipBLASLt workspace)
         torch.cuda.synchronize()
         for _ in range(2):
-            h = runner.model(self.fb)
-            runner.model.compute_logits(h[logits_idx])
+            step_logits()
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            h = runner.model(self.fb)
-            self.logits = runner.model.compute_logits(h[logits_idx])
+            self.logits = step_logits()
 
     def run(self, input_ids, positions, slots, tables, seq_lens) -> torch.Tensor:
         """Lists of b ints and an int32 numpy table [b, <= bt_max]. Rows past
@@ -499,6 +510,27 @@ class ModelRunner:
     @torch.inference_mode()
     def execute(self, out: SchedulerOutput, step: int) -> dict[str, int]:
         """Run one forward + sampling; returns request_id -> sampled token."""
+        # assemble sampling params in the same order as logits rows
+        sample_reqs = [ss.req for ss in out.decode] + [
+            ss.req for ss in out.prefill if ss.samples
+        ]
+        # The samplers read bf16 logits with the results of logits.float();
+        # whatever edits or re-reads logits in fp32 (penalties, logit_bias,
+        # nucleus rejection, JSON mode, top alternatives) gets them widened.
+        need_fp32 = any(
+            (
+                (r.params.presence_penalty or r.params.frequency_penalty)
+                and r.num_generated > 0
+            )
+            or r.params.logit_bias
+            or (
+                (r.params.top_p < 1.0 or r.params.top_k > 0)
+                and r.params.temperature > 0
+            )
+            or r.params.json_mode
+            or r.params.logprobs > 0
+            for r in sample_reqs
+        ) or self.device.type != "cuda"  # the CPU references compute as given
         logits = None
         if (
             self.enable_graphs
@@ -515,12 +547,14 @@ class ModelRunner:
             hidden = self.model(fb)  # [T, H]
             if fb.logits_indices.numel() == 0:
                 return {}
-            logits = self.model.compute_logits(hidden[fb.logits_indices])  # [S, V]
+            rows = hidden[fb.logits_indices]
+            if hasattr(self.model, "forward_logits"):
+                logits = self.model.compute_logits(rows, fp32=need_fp32)
+            else:
+                logits = self.model.compute_logits(rows)  # [S, V]
+        if need_fp32 and logits.dtype != torch.float32:
+            logits = logits.float()
 
-        # assemble sampling params in the same order as logits rows
-        sample_reqs = [ss.req for ss in out.decode] + [
-            ss.req for ss in out.prefill if ss.samples
-        ]
         if logits.shape[0] != len(sample_reqs):
             raise RuntimeError(
                 f"logits rows {logits.shape[0]} != sample reqs {len(sample_reqs)}"

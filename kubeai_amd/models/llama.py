@@ -337,7 +337,18 @@ class DecoderLayer(nn.Module):
                 torch.ones(cfg.hidden_size)
             )
 
-    def forward(self, x, residual, fb, kv_cache, cos_sin):
+    def fp8_fused(self, fb, on_gpu: bool) -> bool:
+        """Whether forward takes the fused-fp8 branch for this batch."""
+        return (
+            not self.post_norms
+            and getattr(self, "_fp8_fused", False)
+            and on_gpu
+            and fb.lora_ids is None
+        )
+
+    def forward(self, x, residual, fb, kv_cache, cos_sin, normed=None):
+        """normed: layer 0 only, the (fp8, row scales) of its input norm when
+        the caller already has them (ops.embed_rmsnorm_fp8)."""
         if self.post_norms:
             # incoming invariant: hidden = x + residual (residual None at
             # layer 0); outgoing (m_normed, hidden_after_attn) keeps it,
@@ -354,17 +365,16 @@ class DecoderLayer(nn.Module):
             )
             mm = ops.rmsnorm(mm, self.post_feedforward_layernorm, self.eps)
             return mm, h2
-        if (
-            getattr(self, "_fp8_fused", False)
-            and x.is_cuda
-            and fb.lora_ids is None
-        ):
+        if self.fp8_fused(fb, x.is_cuda):
             # fp8 serving: norms/activations emit fp8 + per-row scales
             # directly (row_kernels.hip), so activation quantization costs
             # nothing extra; residual stays bf16
             if residual is None:
                 residual = x
-                xq, xs = ops.rmsnorm_fp8(x, self.input_layernorm, self.eps)
+                if normed is not None:
+                    xq, xs = normed
+                else:
+                    xq, xs = ops.rmsnorm_fp8(x, self.input_layernorm, self.eps)
             else:
                 xq, xs = ops.fused_add_rmsnorm_fp8(
                     x, residual, self.input_layernorm, self.eps
@@ -449,37 +459,87 @@ class LlamaForCausalLM(nn.Module):
         else:
             self.cos_sin_local = None
 
-    @torch.inference_mode()
-    def forward(self, fb: ForwardBatch) -> torch.Tensor:
+    def _decoder_stack(self, fb: ForwardBatch):
+        """Embedding and all layers: (x, residual) in front of the final norm."""
         cs = (
             (self.cos_sin, self.cos_sin_local)
             if self.cos_sin_local is not None
             else self.cos_sin
         )
-        x = self.embed_tokens(fb.input_ids.long())
-        if self.cfg.scale_embeddings:
-            # gemma: embeddings scaled by sqrt(hidden), cast to model dtype
-            # first (HF normalizer semantics)
-            x = x * torch.tensor(
-                self.cfg.hidden_size ** 0.5, dtype=x.dtype
+        table = self.embed_tokens.weight
+        l0 = self.layers[0]
+        normed = None
+        if (
+            l0.fp8_fused(fb, table.is_cuda)
+            and not self.cfg.scale_embeddings
+            and not self.cfg.embedding_multiplier
+            and fb.mm_embeds is None
+        ):
+            # layer 0's input norm reads the embedding rows itself: one
+            # launch for the id cast, the gather and rmsnorm_fp8
+            x, xq, xs = ops.embed_rmsnorm_fp8(
+                fb.input_ids, table, l0.input_layernorm, l0.eps
             )
-        elif self.cfg.embedding_multiplier:
-            x = x * self.cfg.embedding_multiplier  # granite
-        if fb.mm_embeds is not None:
-            # image-placeholder positions take the vision-tower embeddings
-            x = x.index_copy(0, fb.mm_idx, fb.mm_embeds.to(x.dtype))
+            normed = (xq, xs)
+        else:
+            x = self.embed_tokens(fb.input_ids.long())
+            if self.cfg.scale_embeddings:
+                # gemma: embeddings scaled by sqrt(hidden), cast to model
+                # dtype first (HF normalizer semantics)
+                x = x * torch.tensor(
+                    self.cfg.hidden_size ** 0.5, dtype=x.dtype
+                )
+            elif self.cfg.embedding_multiplier:
+                x = x * self.cfg.embedding_multiplier  # granite
+            if fb.mm_embeds is not None:
+                # image-placeholder positions take the vision-tower embeddings
+                x = x.index_copy(0, fb.mm_idx, fb.mm_embeds.to(x.dtype))
         residual = None
         for i, layer in enumerate(self.layers):
-            x, residual = layer(x, residual, fb, self.kv_caches[i], cs)
+            x, residual = layer(
+                x, residual, fb, self.kv_caches[i], cs,
+                normed=normed if i == 0 else None,
+            )
+        return x, residual
+
+    @torch.inference_mode()
+    def forward(self, fb: ForwardBatch) -> torch.Tensor:
+        x, residual = self._decoder_stack(fb)
         x, _ = ops.fused_add_rmsnorm(x, residual, self.norm, self.cfg.rms_norm_eps)
         return x
 
     @torch.inference_mode()
-    def compute_logits(self, hidden: torch.Tensor) -> torch.Tensor:
+    def forward_logits(self, fb: ForwardBatch, fp32: bool = True) -> torch.Tensor:
+        """compute_logits(forward(fb), fp32) for a batch whose every row is
+        sampled (the decode graph). With an fp8 lm_head the final norm emits
+        the GEMM's quantized input itself, the bytes and scales that
+        quant_fp8_div would make of the normed rows."""
+        from kubeai_amd.engine.quant import Fp8Linear
+
+        x, residual = self._decoder_stack(fb)
+        if isinstance(self.lm_head, Fp8Linear) and x.is_cuda:
+            xq, xs = ops.fused_add_rmsnorm_fp8_div(
+                x, residual, self.norm, self.cfg.rms_norm_eps
+            )
+            return self._finish_logits(
+                self.lm_head.forward_quantized(xq, xs), fp32
+            )
+        x, _ = ops.fused_add_rmsnorm(x, residual, self.norm, self.cfg.rms_norm_eps)
+        return self.compute_logits(x, fp32)
+
+    @torch.inference_mode()
+    def compute_logits(self, hidden: torch.Tensor, fp32: bool = True) -> torch.Tensor:
+        """fp32=False leaves the logits in the GEMM's bf16 where nothing here
+        edits them: the samplers read bf16 with the results of .float()."""
         if self.lm_head is None:
-            logits = F.linear(hidden, self.embed_tokens.weight).float()
+            logits = F.linear(hidden, self.embed_tokens.weight)
         else:
-            logits = self.lm_head(hidden).float()
+            logits = self.lm_head(hidden)
+        return self._finish_logits(logits, fp32)
+
+    def _finish_logits(self, logits: torch.Tensor, fp32: bool) -> torch.Tensor:
+        if fp32 or self.cfg.logits_scaling or self.cfg.final_logit_softcap > 0:
+            logits = logits.float()
         if self.cfg.logits_scaling:
             logits = logits / self.cfg.logits_scaling  # granite
         cap = self.cfg.final_logit_softcap

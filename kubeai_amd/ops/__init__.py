@@ -399,6 +399,73 @@ def quant_fp8_div(x):
     return ref.quant_fp8_div(x)
 
 
+def _row_kernel_ok(x) -> bool:
+    """A [T, H] tensor the row kernels take as it is."""
+    return (
+        x.is_cuda
+        and x.dtype == torch.bfloat16
+        and x.dim() == 2
+        and x.is_contiguous()
+        and x.shape[1] % 8 == 0
+        and 0 < x.shape[1] <= _QUANT_DIV_MAX_H
+    )
+
+
+def embed_rmsnorm_fp8(ids, table, weight, eps: float):
+    """x = table[ids] followed by rmsnorm_fp8(x, weight, eps): returns
+    (x, fp8 out, row scales), the three byte-equal to that sequence.
+
+    One launch for int32 1-D contiguous ids and a contiguous bf16 table on
+    GPU (the kernel reads row ids[t] itself and clamps the id into the
+    table); the embedding lookup and rmsnorm_fp8 (on CPU: the reference
+    norm and quantization) for every other input."""
+    if (
+        _row_kernel_ok(table)
+        and ids.is_cuda
+        and ids.dtype == torch.int32
+        and ids.dim() == 1
+        and ids.is_contiguous()
+        and weight.dtype == torch.bfloat16
+    ):
+        _require_ext()
+        T, H = ids.shape[0], table.shape[1]
+        x = torch.empty((T, H), dtype=table.dtype, device=table.device)
+        out, scale = _empty_fp8_rows((T, H), table.device)
+        _C.embed_rmsnorm_fp8(out, scale, x, ids, table, weight, eps)
+        return x, out, scale
+    x = torch.nn.functional.embedding(ids.long(), table)
+    if x.is_cuda:
+        return (x, *rmsnorm_fp8(x, weight, eps))
+    return (x, *ref.quant_fp8(ref.rmsnorm(x, weight, eps)))
+
+
+def fused_add_rmsnorm_fp8_div(x, residual, weight, eps: float,
+                              write_rows: bool = False):
+    """quant_fp8_div(fused_add_rmsnorm(x, residual, weight, eps)[0]):
+    (e4m3 [T, H], fp32 scales [T, 1]), byte-equal to the two ops.
+
+    One launch for 2-D contiguous bf16 on GPU. With write_rows it also
+    updates x and residual in place as fused_add_rmsnorm does; without it
+    the kernel only reads them. Every other input runs the two ops (which on
+    GPU update x and residual), so a caller that passes write_rows=False
+    must not read either afterwards."""
+    if (
+        _row_kernel_ok(x)
+        and residual.is_contiguous()
+        and residual.shape == x.shape
+        and residual.dtype == x.dtype
+        and weight.dtype == torch.bfloat16
+    ):
+        _require_ext()
+        out, scale = _empty_fp8_rows(x.shape, x.device)
+        _C.fused_add_rmsnorm_fp8_div(
+            out, scale, x, residual, weight, eps, write_rows
+        )
+        return out, scale.view(-1, 1)
+    y, _ = fused_add_rmsnorm(x, residual, weight, eps)
+    return quant_fp8_div(y)
+
+
 def greedy_sample(logits):
     if logits.is_cuda:
         _require_ext()
@@ -474,7 +541,8 @@ def gumbel_sample_logprob(logits, temperature, seeds, step: int) -> SampleResult
 def token_logprobs(logits, tokens):
     """(logprob [B], lse [B]) of int64 tokens[b] in row b of fp32 logits, for
     tokens that do not come from a *_sample_logprob op. One launch on GPU;
-    lse is bit-identical to the one those ops return."""
+    lse is bit-identical to the one those ops return. Like the samplers, the
+    GPU kernel also takes bf16 logits, with the results of logits.float()."""
     if logits.is_cuda:
         _require_ext()
         B = logits.shape[0]
