@@ -1,6 +1,7 @@
 // Python bindings for the kubeai_amd gfx950 HIP kernels.
 #include <torch/extension.h>
 
+#include <tuple>
 #include <utility>
 
 #include "attention_plan.h"
@@ -50,6 +51,15 @@ void int4_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor qp,
                torch::Tensor sp, torch::Tensor zp, int64_t N, int64_t K,
                int64_t group);
 int64_t int4_gemm_tiles(int64_t N, int64_t M);
+// grouped MoE expert GEMMs routed on the device (int4_moe.hip); table is the
+// int64 [E, 3] of the experts' (qp, sp, zp) addresses
+void int4_moe_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor selected,
+                   torch::Tensor table, int64_t row_div, int64_t E, int64_t N,
+                   int64_t K, int64_t group, int64_t n_tiles);
+void moe_combine(torch::Tensor out, torch::Tensor y, torch::Tensor selected,
+                 torch::Tensor weights, int64_t E);
+std::tuple<int64_t, int64_t> int4_moe_plan(int64_t N, int64_t T, int64_t E,
+                                           int64_t k);
 void greedy_sample(torch::Tensor out, torch::Tensor logits);
 void gumbel_sample(torch::Tensor out, torch::Tensor logits,
                    torch::Tensor temperature, torch::Tensor seeds,
@@ -152,6 +162,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("int4_gemm_tiles", &int4_gemm_tiles,
         "16-column tiles per workgroup int4_gemm launches with",
         pybind11::arg("N"), pybind11::arg("M"));
+  m.def("int4_moe_gemm", &int4_moe_gemm,
+        "y[t*k+j] = x[(t*k+j) / row_div] @ W[selected[t,j]]^T over packed int4 "
+        "experts, T <= 64; n_tiles = 0 takes int4_moe_plan's",
+        pybind11::arg("y"), pybind11::arg("x"), pybind11::arg("selected"),
+        pybind11::arg("table"), pybind11::arg("row_div"), pybind11::arg("E"),
+        pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("group"),
+        pybind11::arg("n_tiles") = 0);
+  m.def("moe_combine", &moe_combine,
+        "out[t] = sum_j weights[t,j] * y[t*k+j] in ascending expert id, bf16 "
+        "steps; ids outside [0, E) are skipped (E = 0: no upper limit)",
+        pybind11::arg("out"), pybind11::arg("y"), pybind11::arg("selected"),
+        pybind11::arg("weights"), pybind11::arg("E") = 0);
+  m.def("int4_moe_plan", &int4_moe_plan,
+        "(16-row tiles, 16-column tiles per workgroup) int4_moe_gemm launches "
+        "with", pybind11::arg("N"), pybind11::arg("T"), pybind11::arg("E"),
+        pybind11::arg("k"));
   m.def("greedy_sample", &greedy_sample, "argmax sampling");
   m.def("gumbel_sample", &gumbel_sample, "temperature sampling (hash RNG)");
   m.def("greedy_sample_logprob", &greedy_sample_logprob,

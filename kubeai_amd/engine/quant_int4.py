@@ -5,7 +5,9 @@ Asymmetric 4-bit codes with one fp16 scale and one 4-bit zero point per
 stays packed in HBM (0.5 + 2.5/g bytes per weight instead of 2); decode
 GEMMs (M <= ops.INT4_M_FUSED) dequantize in registers inside the fused
 gfx950 kernel (csrc/int4_gemm.hip), larger M dequantize into a shared
-bf16 workspace and run the library GEMM.
+bf16 workspace and run the library GEMM. The experts of a MoE block are
+served together by the grouped kernel (csrc/int4_moe.hip) through an
+Int4ExpertGroup.
 
 The pinned dequantization, the exact expression and rounding of
 models/loader._awq_dequant:
@@ -221,6 +223,82 @@ class Int4Linear(nn.Module):
         return y
 
 
+class Int4ExpertGroup:
+    """The E Int4Weights of one MoE projection (every expert's gate_up_proj,
+    or every expert's down_proj) as the grouped kernel takes them: the
+    weights themselves, not a copy, and `table`, an int64 [E, 3] tensor on
+    their device holding each expert's (qp, sp, zp) address.
+
+    All experts share N, K, group size and device. The table is built here,
+    when the experts are converted or moved; ops.int4_moe_linear only reads
+    it (that call can run under graph capture, where building it would be a
+    host-to-device copy inside the capture)."""
+
+    def __init__(self, weights: list[Int4Weight]):
+        if not weights:
+            raise ValueError("int4 expert group: no experts")
+        w0 = weights[0]
+        for e, w in enumerate(weights):
+            if (w.N, w.K, w.group) != (w0.N, w0.K, w0.group):
+                raise ValueError(
+                    f"int4 expert group: expert {e} is [{w.N}, {w.K}] "
+                    f"g={w.group}, expert 0 is [{w0.N}, {w0.K}] g={w0.group}"
+                )
+            if w.device != w0.device:
+                raise ValueError(
+                    f"int4 expert group: expert {e} is on {w.device}, "
+                    f"expert 0 on {w0.device}"
+                )
+            if not (w.qp.is_contiguous() and w.sp.is_contiguous()
+                    and w.zp.is_contiguous()) or w.qp.data_ptr() % 16:
+                raise ValueError(
+                    f"int4 expert group: expert {e}'s packed tensors must be "
+                    "contiguous and its codes 16-byte aligned"
+                )
+        self.weights = list(weights)
+        self.E = len(weights)
+        self.N, self.K, self.group = w0.N, w0.K, w0.group
+        self.table = torch.tensor(
+            [[w.qp.data_ptr(), w.sp.data_ptr(), w.zp.data_ptr()]
+             for w in weights],
+            dtype=torch.int64,
+        ).to(w0.device)
+
+    @property
+    def device(self):
+        return self.weights[0].device
+
+    def table_on(self, device) -> torch.Tensor:
+        if self.table.device != device:
+            raise RuntimeError(
+                f"int4 expert group lives on {self.table.device}, the call "
+                f"is on {device}"
+            )
+        return self.table
+
+    def holds(self, linears) -> bool:
+        """Whether the group still describes exactly these Int4Linears'
+        buffers (a buffer that was replaced leaves the table stale)."""
+        return len(linears) == self.E and all(
+            w.qp is lin.qweight and w.sp is lin.scales and w.zp is lin.qzeros
+            for w, lin in zip(self.weights, linears)
+        )
+
+
+def expert_groups(experts):
+    """(gate_up group, down group) of a list of expert MLPs when every
+    projection is a bias-free Int4Linear, else None."""
+    gate_up = [getattr(ex, "gate_up_proj", None) for ex in experts]
+    down = [getattr(ex, "down_proj", None) for ex in experts]
+    for lin in gate_up + down:
+        if not isinstance(lin, Int4Linear) or lin.bias is not None:
+            return None
+    return (
+        Int4ExpertGroup([lin.int4 for lin in gate_up]),
+        Int4ExpertGroup([lin.int4 for lin in down]),
+    )
+
+
 # lm_head stays bf16, as in AWQ checkpoints
 _TARGETS = ("qkv_proj", "o_proj", "gate_up_proj", "down_proj")
 
@@ -241,4 +319,10 @@ def convert_to_int4(model: nn.Module, group: int = 128) -> int:
                 raise ValueError(f"{mod_name}.{name}: {e}") from None
             setattr(mod, name, Int4Linear(w, child.bias))
             n += 1
+    # MoE blocks: the grouped kernel's address tables, built now that every
+    # expert is in place
+    for mod in model.modules():
+        refresh = getattr(mod, "refresh_int4_groups", None)
+        if refresh is not None:
+            refresh()
     return n

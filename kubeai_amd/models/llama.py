@@ -261,12 +261,49 @@ class MoEMLP(nn.Module):
         self.top_k = cfg.num_experts_per_tok
         self.gate = nn.Linear(cfg.hidden_size, self.n_experts, bias=False)
         self.experts = nn.ModuleList([MLP(cfg) for _ in range(self.n_experts)])
+        self._int4_groups = None
+
+    def _apply(self, fn, *args, **kwargs):
+        # .to()/.cuda(): the experts' buffers moved, so the address tables
+        # of the grouped int4 kernel are rebuilt now, not at the next forward
+        super()._apply(fn, *args, **kwargs)
+        self.refresh_int4_groups()
+        return self
+
+    def refresh_int4_groups(self):
+        """(gate_up, down) Int4ExpertGroups when the experts are bias-free
+        int4 SwiGLU MLPs, else None. Called when the experts are converted
+        or moved."""
+        self._int4_groups = None
+        if not any(ex.gelu for ex in self.experts):
+            from kubeai_amd.engine.quant_int4 import expert_groups
+
+            self._int4_groups = expert_groups(self.experts)
+        return self._int4_groups
+
+    def int4_groups(self):
+        groups = self._int4_groups
+        if groups is not None and not (
+            groups[0].holds([ex.gate_up_proj for ex in self.experts])
+            and groups[1].holds([ex.down_proj for ex in self.experts])
+        ):
+            groups = self.refresh_int4_groups()  # a buffer was replaced
+        return groups
 
     def forward(self, x: torch.Tensor, fb: ForwardBatch | None = None) -> torch.Tensor:
         T, H = x.shape
         router = F.linear(x.float(), self.gate.weight.float())  # [T, E]
         weights, selected = torch.topk(router, self.top_k, dim=-1)
         weights = torch.softmax(weights, dim=-1).to(x.dtype)  # [T, k]
+        if x.is_cuda and 1 <= T <= min(ops.INT4_MOE_T, 64):
+            # int4 experts at decode sizes: grouped GEMMs that read the
+            # routing on the device. Static shapes like the dense loop below
+            # (so it captures), the same bits, 4 launches instead of 5 per
+            # expert, and only the routed experts' weights are read
+            # (docs/kernels.md, profiles/r10_int4_moe.md).
+            groups = self.int4_groups()
+            if groups is not None:
+                return ops.int4_moe_mlp(x, selected, weights, *groups)
         if T <= 256:
             # decode-sized batches: run EVERY expert densely. At these M
             # the expert GEMMs are weight-bound, and a batch this size

@@ -331,6 +331,71 @@ def int4_linear(x, w):
     return torch.nn.functional.linear(x, dense)
 
 
+# ---------------- int4 MoE: grouped expert GEMMs, routed on the device ------
+# `group` below is an engine.quant_int4.Int4ExpertGroup (the E Int4Weights of
+# one projection and the device table of their addresses); `selected` is
+# torch.topk's int64 [T, k].
+
+# Largest T for which MoEMLP takes int4_moe_mlp; above it, and at 0, it keeps
+# the dense expert loop. See docs/kernels.md for how it is set.
+INT4_MOE_T = int(os.environ.get("KUBEAI_INT4_MOE_T", "64"))
+
+
+def int4_moe_linear(x, selected, group, row_div: int, out=None):
+    """y[t*k + j] = x[(t*k + j) // row_div] @ W[selected[t, j]]^T, bf16
+    [T*k, N], one launch for all experts. row_div = k: the k pairs of a token
+    share its row of x [T, K]; row_div = 1: x is [T*k, K]. Every row is
+    bit-equal to int4_linear's for that row and expert. T <= 64."""
+    if not x.is_cuda:
+        res = ref.moe_linear(
+            x, selected, [w.dequant() for w in group.weights], row_div
+        )
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+    _require_ext()
+    if x.dim() == 2 and (x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16):
+        x = x.contiguous()
+    if out is None:
+        out = torch.empty(
+            (selected.numel(), group.N), dtype=torch.bfloat16, device=x.device
+        )
+    _C.int4_moe_gemm(
+        out, x, selected, group.table_on(x.device), row_div, group.E, group.N,
+        group.K, group.group,
+    )
+    return out
+
+
+def moe_combine(y, selected, weights, n_experts: int | None = None):
+    """out[t] = sum_j weights[t, j] * y[t*k + j] -> [T, H], added up as
+    MoEMLP's dense loop does (ref.moe_combine). One launch on GPU."""
+    if not y.is_cuda:
+        return ref.moe_combine(y, selected, weights, n_experts)
+    _require_ext()
+    out = torch.empty(
+        (selected.shape[0], y.shape[1]), dtype=y.dtype, device=y.device
+    )
+    _C.moe_combine(out, y, selected, weights, n_experts or 0)
+    return out
+
+
+def int4_moe_mlp(x, selected, weights, gate_up_group, down_group):
+    """The SwiGLU MoE block over int4 experts: [T, H] -> [T, H], equal to
+    MoEMLP's dense loop. Four launches on GPU (gate_up, silu_and_mul, down,
+    combine), and only the routed experts' weights are read."""
+    if not x.is_cuda:
+        return ref.moe_mlp(
+            x, selected, weights,
+            [w.dequant() for w in gate_up_group.weights],
+            [w.dequant() for w in down_group.weights],
+        )
+    h = int4_moe_linear(x, selected, gate_up_group, selected.shape[1])
+    y = int4_moe_linear(silu_and_mul(h), selected, down_group, 1)
+    return moe_combine(y, selected, weights, gate_up_group.E)
+
+
 def _empty_fp8_rows(shape, device):
     """Uninitialised (e4m3 `shape`, f32 [shape[0]] row scales) for an fp8
     producer to fill."""

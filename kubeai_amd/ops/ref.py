@@ -273,6 +273,68 @@ def gelu_and_mul(x: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------
+# MoE over per-expert weights (the int4 grouped path's reference)
+# ---------------------------------------------------------------------------
+
+def _gather_pairs(per_expert: torch.Tensor, selected: torch.Tensor,
+                  row_div: int) -> torch.Tensor:
+    """per_expert [E, R, N] -> [T*k, N]: pair p = t*k + j takes row
+    p // row_div of expert selected[t, j]."""
+    n_pairs = selected.numel()
+    rows = torch.arange(n_pairs, device=selected.device) // row_div
+    return per_expert[selected.reshape(-1), rows]
+
+
+def moe_linear(x, selected, expert_weights, row_div: int) -> torch.Tensor:
+    """y[t*k + j] = x[(t*k + j) // row_div] @ expert_weights[selected[t, j]]^T.
+    Every expert runs on ALL rows of x and the pairs are gathered afterwards:
+    F.linear promises no row independence, so gathering first would not be
+    the dense loop's arithmetic."""
+    per_expert = torch.stack(
+        [torch.nn.functional.linear(x, w) for w in expert_weights]
+    )
+    return _gather_pairs(per_expert, selected, row_div)
+
+
+def moe_combine(y, selected, weights, n_experts: int | None = None):
+    """out[t] = sum_j weights[t, j] * y[t*k + j] as MoEMLP's dense loop adds
+    it up: pairs in ascending expert id, every product and every partial sum
+    rounded to the dtype of y, the first term taken as it is. Ids outside
+    [0, n_experts) are skipped."""
+    T, k = selected.shape
+    order = selected.argsort(dim=1, stable=True)
+    ids = selected.gather(1, order)
+    w = weights.gather(1, order)
+    yk = y.view(T, k, -1).gather(
+        1, order.unsqueeze(-1).expand(T, k, y.shape[-1])
+    )
+    valid = ids >= 0
+    if n_experts is not None:
+        valid &= ids < n_experts
+    out = torch.zeros_like(yk[:, 0])
+    seen = torch.zeros(T, 1, dtype=torch.bool, device=y.device)
+    for j in range(k):
+        term = yk[:, j] * w[:, j : j + 1]
+        v = valid[:, j : j + 1]
+        out = torch.where(v, torch.where(seen, out + term, term), out)
+        seen = seen | v
+    return out
+
+
+def moe_mlp(x, selected, weights, gate_up_weights, down_weights):
+    """The SwiGLU MoE block over per-expert [2I, H] and [H, I] weights, each
+    expert evaluated on all T rows as the dense loop does."""
+    per_expert = torch.stack([
+        torch.nn.functional.linear(
+            silu_and_mul(torch.nn.functional.linear(x, gu)), dn
+        )
+        for gu, dn in zip(gate_up_weights, down_weights)
+    ])
+    y = _gather_pairs(per_expert, selected, selected.shape[1])
+    return moe_combine(y, selected, weights, len(gate_up_weights))
+
+
+# ---------------------------------------------------------------------------
 # sampling
 # ---------------------------------------------------------------------------
 
