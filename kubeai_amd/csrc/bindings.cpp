@@ -60,6 +60,13 @@ void moe_combine(torch::Tensor out, torch::Tensor y, torch::Tensor selected,
                  torch::Tensor weights, int64_t E);
 std::tuple<int64_t, int64_t> int4_moe_plan(int64_t N, int64_t T, int64_t E,
                                            int64_t k);
+// the fp8 sibling (fp8_moe.hip); table is the int64 [E, 2] of the experts'
+// (weight_fp8, weight_scale) addresses
+void fp8_moe_gemm(torch::Tensor y, torch::Tensor xq, torch::Tensor xs,
+                  torch::Tensor selected, torch::Tensor table, int64_t row_div,
+                  int64_t E, int64_t N, int64_t K, int64_t n_tiles);
+std::tuple<int64_t, int64_t> fp8_moe_plan(int64_t N, int64_t T, int64_t E,
+                                          int64_t k);
 void greedy_sample(torch::Tensor out, torch::Tensor logits);
 void gumbel_sample(torch::Tensor out, torch::Tensor logits,
                    torch::Tensor temperature, torch::Tensor seeds,
@@ -176,6 +183,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("weights"), pybind11::arg("E") = 0);
   m.def("int4_moe_plan", &int4_moe_plan,
         "(16-row tiles, 16-column tiles per workgroup) int4_moe_gemm launches "
+        "with", pybind11::arg("N"), pybind11::arg("T"), pybind11::arg("E"),
+        pybind11::arg("k"));
+  m.def("fp8_moe_gemm", &fp8_moe_gemm,
+        "y[t*k+j] = bf16(xq[(t*k+j) / row_div] @ wq_e^T * xs * ws_e), e = "
+        "selected[t,j], over e4m3 experts, T <= 64; n_tiles = 0 takes "
+        "fp8_moe_plan's",
+        pybind11::arg("y"), pybind11::arg("xq"), pybind11::arg("xs"),
+        pybind11::arg("selected"), pybind11::arg("table"),
+        pybind11::arg("row_div"), pybind11::arg("E"), pybind11::arg("N"),
+        pybind11::arg("K"), pybind11::arg("n_tiles") = 0);
+  m.def("fp8_moe_plan", &fp8_moe_plan,
+        "(16-row tiles, 16-column tiles per workgroup) fp8_moe_gemm launches "
         "with", pybind11::arg("N"), pybind11::arg("T"), pybind11::arg("E"),
         pybind11::arg("k"));
   m.def("greedy_sample", &greedy_sample, "argmax sampling");

@@ -26,31 +26,18 @@
 #include "common.h"
 #include "dispatch.h"
 #include "int4_common.h"
+#include "moe_routing.h"
 
 using namespace w4a16;
+using moe::dispatch_live;
+using moe::kMaxPairs;
+using moe::kMaxRows;
+using moe::kMaxTopK;
+using moe::ListedRows;
 
 namespace {
 
-constexpr int kMaxRows = 64;                    // pairs one expert can take
-constexpr int kMaxPairs = kWaves * WAVE_SIZE;   // one routing entry per thread
-constexpr int kMaxTopK = 8;
-
-// rows 0 .. count-1 of the workgroup's tiles are the listed pairs' rows of y
-struct ListedRows {
-  const int* list;
-  int count;
-  DEV_INLINE bool stored(const int r) const { return r < count; }
-  DEV_INLINE int row(const int r) const { return list[r]; }
-};
-
-// f(Int<LT>) for LT = min(live, MT), live >= 1 and wave-uniform
-template <int MT, typename F>
-DEV_INLINE void dispatch_live(const int live, F&& f) {
-  if constexpr (MT > 1) {
-    if (live < MT) return dispatch_live<MT - 1>(live, f);
-  }
-  f(Int<MT>{});
-}
+static_assert(kWaves == moe::kWaves, "the pair list is built by 8 waves");
 
 template <int MT, int NT, int G>
 __launch_bounds__(kWaves * WAVE_SIZE) __global__ void int4_moe_gemm_kernel(
@@ -67,27 +54,11 @@ __launch_bounds__(kWaves * WAVE_SIZE) __global__ void int4_moe_gemm_kernel(
   const int lane = threadIdx.x % WAVE_SIZE;
   const int nl = lane & 15, kq = lane >> 4;
 
-  // The pairs of this expert, in ascending pair order: thread p tests entry
-  // p (n_pairs <= kMaxPairs), a ballot and the waves' counts give its place.
-  // The list is cut at kMaxRows, so any content of `selected` stays inside
-  // it; an id outside [0, E) matches no workgroup.
+  // the pairs of this expert, in ascending pair order (moe_routing.h)
   __shared__ int list[kMaxRows];
   __shared__ int wave_hits[kWaves];
-  const int p = threadIdx.x;
-  const bool hit = p < n_pairs && selected[p] == (int64_t)expert;
-  const unsigned long long hits = __ballot(hit);
-  if (lane == 0) wave_hits[wave] = __popcll(hits);
-  __syncthreads();
-  int before = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int c = wave_hits[w];
-    if (w < wave) before += c;
-    total += c;
-  }
-  const int pos = before + __popcll(hits & ((1ull << lane) - 1ull));
-  if (hit && pos < kMaxRows) list[pos] = p;
-  const int count = __builtin_amdgcn_readfirstlane(min(total, kMaxRows));
+  const int count = moe::build_pair_list(list, wave_hits, selected, n_pairs,
+                                         expert, wave, lane);
   if (count == 0) return;  // the whole workgroup: no weight is touched
   __syncthreads();
 

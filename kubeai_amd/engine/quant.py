@@ -81,6 +81,95 @@ class Fp8Linear(nn.Module):
         )
 
 
+class Fp8ExpertGroup:
+    """The E Fp8Linears of one MoE projection (every expert's gate_up_proj,
+    or every expert's down_proj) as the grouped kernel (csrc/fp8_moe.hip)
+    takes them: the modules themselves, not a copy of their weights, and
+    `table`, an int64 [E, 2] tensor on their device holding each expert's
+    (weight_fp8, weight_scale) address.
+
+    All experts share N, K and device and have no bias. The table is built
+    here, when the experts are converted or moved; ops.fp8_moe_linear only
+    reads it (that call can run under graph capture, where building it would
+    be a host-to-device copy inside the capture)."""
+
+    def __init__(self, linears: list[Fp8Linear]):
+        if not linears:
+            raise ValueError("fp8 expert group: no experts")
+        for e, lin in enumerate(linears):
+            if not isinstance(lin, Fp8Linear):
+                raise ValueError(
+                    f"fp8 expert group: expert {e} is a "
+                    f"{type(lin).__name__}, not an Fp8Linear"
+                )
+            if lin.bias is not None:
+                raise ValueError(f"fp8 expert group: expert {e} has a bias")
+        w0 = linears[0].weight_fp8
+        for e, lin in enumerate(linears):
+            w, s = lin.weight_fp8, lin.weight_scale
+            if w.dim() != 2 or w.shape != w0.shape or s.numel() != w.shape[0]:
+                raise ValueError(
+                    f"fp8 expert group: expert {e} is {list(w.shape)} with "
+                    f"{s.numel()} scales, expert 0 is {list(w0.shape)}"
+                )
+            if w.dtype != FP8_DTYPE or s.dtype != torch.float32:
+                raise ValueError(
+                    f"fp8 expert group: expert {e} holds {w.dtype} weights "
+                    f"and {s.dtype} scales, need {FP8_DTYPE} and float32"
+                )
+            if w.device != w0.device or s.device != w0.device:
+                raise ValueError(
+                    f"fp8 expert group: expert {e} is on {w.device} (scales "
+                    f"on {s.device}), expert 0 on {w0.device}"
+                )
+            if not (w.is_contiguous() and s.is_contiguous()) or w.data_ptr() % 16:
+                raise ValueError(
+                    f"fp8 expert group: expert {e}'s weight and scales must "
+                    "be contiguous and the weight 16-byte aligned"
+                )
+        self.linears = list(linears)
+        # the tensors the table points at: holds() compares against these
+        self._tensors = [(lin.weight_fp8, lin.weight_scale) for lin in linears]
+        self.E = len(linears)
+        self.N, self.K = w0.shape
+        self.table = torch.tensor(
+            [[w.data_ptr(), s.data_ptr()] for w, s in self._tensors],
+            dtype=torch.int64,
+        ).to(w0.device)
+
+    @property
+    def device(self):
+        return self._tensors[0][0].device
+
+    def table_on(self, device) -> torch.Tensor:
+        if self.table.device != device:
+            raise RuntimeError(
+                f"fp8 expert group lives on {self.table.device}, the call "
+                f"is on {device}"
+            )
+        return self.table
+
+    def holds(self, modules) -> bool:
+        """Whether the group still describes exactly these modules' buffers
+        (a buffer that was replaced leaves the table stale)."""
+        return len(modules) == self.E and all(
+            isinstance(lin, Fp8Linear)
+            and w is lin.weight_fp8 and s is lin.weight_scale
+            for (w, s), lin in zip(self._tensors, modules)
+        )
+
+
+def fp8_expert_groups(experts):
+    """(gate_up group, down group) of a list of expert MLPs when every
+    projection is a bias-free Fp8Linear, else None."""
+    gate_up = [getattr(ex, "gate_up_proj", None) for ex in experts]
+    down = [getattr(ex, "down_proj", None) for ex in experts]
+    for lin in gate_up + down:
+        if not isinstance(lin, Fp8Linear) or lin.bias is not None:
+            return None
+    return Fp8ExpertGroup(gate_up), Fp8ExpertGroup(down)
+
+
 _TARGETS = ("qkv_proj", "o_proj", "gate_up_proj", "down_proj", "lm_head")
 
 
@@ -109,4 +198,10 @@ def convert_to_fp8(model: nn.Module) -> int:
             # MoE: attention runs the fused-fp8 path; the MLP input stays
             # bf16 (router needs it) and MoEMLP quantizes once itself
             layer._fp8_fused = True
+    # MoE blocks: the grouped kernel's address tables, built now that every
+    # expert is in place
+    for mod in model.modules():
+        refresh = getattr(mod, "refresh_fp8_groups", None)
+        if refresh is not None:
+            refresh()
     return n

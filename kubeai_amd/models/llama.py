@@ -262,13 +262,36 @@ class MoEMLP(nn.Module):
         self.gate = nn.Linear(cfg.hidden_size, self.n_experts, bias=False)
         self.experts = nn.ModuleList([MLP(cfg) for _ in range(self.n_experts)])
         self._int4_groups = None
+        self._fp8_groups = None
 
     def _apply(self, fn, *args, **kwargs):
         # .to()/.cuda(): the experts' buffers moved, so the address tables
-        # of the grouped int4 kernel are rebuilt now, not at the next forward
+        # of the grouped int4 and fp8 kernels are rebuilt now, not at the
+        # next forward
         super()._apply(fn, *args, **kwargs)
         self.refresh_int4_groups()
+        self.refresh_fp8_groups()
         return self
+
+    def refresh_fp8_groups(self):
+        """(gate_up, down) Fp8ExpertGroups when the experts are bias-free
+        fp8 SwiGLU MLPs, else None. Called when the experts are converted
+        or moved."""
+        self._fp8_groups = None
+        if not any(ex.gelu for ex in self.experts):
+            from kubeai_amd.engine.quant import fp8_expert_groups
+
+            self._fp8_groups = fp8_expert_groups(self.experts)
+        return self._fp8_groups
+
+    def fp8_groups(self):
+        groups = self._fp8_groups
+        if groups is not None and not (
+            groups[0].holds([ex.gate_up_proj for ex in self.experts])
+            and groups[1].holds([ex.down_proj for ex in self.experts])
+        ):
+            groups = self.refresh_fp8_groups()  # a buffer was replaced
+        return groups
 
     def refresh_int4_groups(self):
         """(gate_up, down) Int4ExpertGroups when the experts are bias-free
@@ -304,6 +327,14 @@ class MoEMLP(nn.Module):
             groups = self.int4_groups()
             if groups is not None:
                 return ops.int4_moe_mlp(x, selected, weights, *groups)
+        if x.is_cuda and 1 <= T <= ops.fp8_moe_t():
+            # fp8 experts, behind KUBEAI_FP8_MOE_T (off by default): the same
+            # four launches over e4m3 weights. Not the dense loop's bits: the
+            # fp32 sums run in another order than _scaled_mm's
+            # (docs/kernels.md, profiles/r11_fp8_moe.md).
+            groups = self.fp8_groups()
+            if groups is not None:
+                return ops.fp8_moe_mlp(x, selected, weights, *groups)
         if T <= 256:
             # decode-sized batches: run EVERY expert densely. At these M
             # the expert GEMMs are weight-bound, and a batch this size

@@ -396,6 +396,70 @@ def int4_moe_mlp(x, selected, weights, gate_up_group, down_group):
     return moe_combine(y, selected, weights, gate_up_group.E)
 
 
+# ---------------- fp8 MoE: grouped expert GEMMs, routed on the device -------
+# `group` below is an engine.quant.Fp8ExpertGroup (the E Fp8Linears of one
+# projection and the device table of their addresses).
+
+
+def fp8_moe_t() -> int:
+    """Largest T for which MoEMLP takes fp8_moe_mlp: KUBEAI_FP8_MOE_T, 0 (the
+    dense expert loop at every T) when unset, at most 64. The grouped path
+    sums in another order than the dense loop's _scaled_mm, so it is opt-in
+    (profiles/r11_fp8_moe.md). Read at call time: the tests and A/B runs flip
+    it."""
+    try:
+        limit = int(os.environ.get("KUBEAI_FP8_MOE_T", "0"))
+    except ValueError:
+        return 0
+    return max(0, min(limit, 64))
+
+
+def fp8_moe_linear(xq, xs, selected, group, row_div: int, out=None):
+    """y[t*k + j] = bf16((xq[r] @ wq_e^T) * xs[r] * ws_e) with r =
+    (t*k + j) // row_div and e = selected[t, j]: bf16 [T*k, N], one launch for
+    all experts. xq is e4m3 [R, K] with fp32 row scales xs [R]. row_div = k:
+    the k pairs of a token share its row; row_div = 1: xq is [T*k, K]. Every
+    row is Fp8Linear.forward_quantized's for that row and expert up to the
+    order of the fp32 sum, and has the same bits whatever else is in the
+    batch. T <= 64."""
+    if not xq.is_cuda:
+        res = ref.fp8_moe_linear(
+            xq, xs, selected,
+            [(lin.weight_fp8, lin.weight_scale) for lin in group.linears],
+            row_div,
+        )
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+    _require_ext()
+    if xq.dim() == 2 and (
+        xq.stride(1) != 1 or xq.stride(0) % 16 or xq.data_ptr() % 16
+    ):
+        xq = xq.contiguous()
+    if out is None:
+        out = torch.empty(
+            (selected.numel(), group.N), dtype=torch.bfloat16, device=xq.device
+        )
+    _C.fp8_moe_gemm(
+        out, xq, xs.reshape(-1), selected, group.table_on(xq.device), row_div,
+        group.E, group.N, group.K,
+    )
+    return out
+
+
+def fp8_moe_mlp(x, selected, weights, gate_up_group, down_group):
+    """The SwiGLU MoE block over fp8 experts: [T, H] -> [T, H]. The dense
+    loop's operations on the routed pairs only: quant_fp8, gate_up,
+    silu_and_mul_fp8, down, combine. Five launches on GPU, and only the
+    routed experts' weights are read."""
+    xq, xs = quant_fp8(x)
+    h = fp8_moe_linear(xq, xs, selected, gate_up_group, selected.shape[1])
+    a8, a_scale = silu_and_mul_fp8(h)
+    y = fp8_moe_linear(a8, a_scale, selected, down_group, 1)
+    return moe_combine(y, selected, weights, gate_up_group.E)
+
+
 def _empty_fp8_rows(shape, device):
     """Uninitialised (e4m3 `shape`, f32 [shape[0]] row scales) for an fp8
     producer to fill."""

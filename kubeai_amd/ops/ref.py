@@ -296,6 +296,19 @@ def moe_linear(x, selected, expert_weights, row_div: int) -> torch.Tensor:
     return _gather_pairs(per_expert, selected, row_div)
 
 
+def fp8_moe_linear(xq, xs, selected, expert_weights, row_div: int):
+    """moe_linear over fp8 experts: expert_weights is a list of (e4m3 [N, K],
+    fp32 scales of N elements), xq e4m3 [R, K] with fp32 row scales xs [R].
+    Per expert it is Fp8Linear.forward_quantized's CPU fallback: dequantize
+    both sides, multiply in fp32, round to bf16."""
+    x = xq.float() * xs.reshape(-1, 1)
+    per_expert = torch.stack([
+        (x @ (wq.float() * ws.reshape(-1, 1)).t()).to(torch.bfloat16)
+        for wq, ws in expert_weights
+    ])
+    return _gather_pairs(per_expert, selected, row_div)
+
+
 def moe_combine(y, selected, weights, n_experts: int | None = None):
     """out[t] = sum_j weights[t, j] * y[t*k + j] as MoEMLP's dense loop adds
     it up: pairs in ascending expert id, every product and every partial sum
