@@ -81,6 +81,12 @@ void token_logprobs(torch::Tensor out_logprob, torch::Tensor out_lse,
                     torch::Tensor logits, torch::Tensor tokens);
 void sgmv(torch::Tensor y, torch::Tensor x, torch::Tensor A, torch::Tensor B,
           torch::Tensor idx, double scale);
+// batched multi-LoRA apply routed on the device (lora_batched.hip); table is
+// the int64 [S, 4] of the slots' (A address, B address, R, scale bits)
+void lora_apply(torch::Tensor y, torch::Tensor x, torch::Tensor slots,
+                torch::Tensor table, torch::Tensor table_host,
+                torch::Tensor vpart, int64_t ks);
+std::tuple<int64_t, int64_t> lora_plan(int64_t T, int64_t K);
 void register_chwbl(pybind11::module_& m);
 // one-shot fused all-reduce over xGMI (allreduce.hip)
 pybind11::bytes xgmi_alloc();
@@ -228,5 +234,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xgmi_max_elems", &xgmi_max_elems, "one-shot capacity (bf16 elems)");
   m.def("xgmi_shutdown", &xgmi_shutdown, "free/close comm buffers");
   m.def("sgmv", &sgmv, "segmented gather LoRA apply (one adapter segment)");
+  m.def("lora_apply", &lora_apply,
+        "y[t] += B_s (scale_s * A_s x[t]) for s = slots[t] >= 1, every adapter "
+        "of the batch in two launches, T <= 64; ks = 0 takes lora_plan's",
+        pybind11::arg("y"), pybind11::arg("x"), pybind11::arg("slots"),
+        pybind11::arg("table"), pybind11::arg("table_host"),
+        pybind11::arg("vpart"), pybind11::arg("ks") = 0);
+  m.def("lora_plan", &lora_plan,
+        "(16-row tiles, K splits) lora_apply launches with",
+        pybind11::arg("T"), pybind11::arg("K"));
   register_chwbl(m);
 }

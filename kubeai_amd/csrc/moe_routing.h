@@ -33,12 +33,15 @@ struct ListedRows {
 // id outside [0, E) matches no workgroup. Called by all kWaves * WAVE_SIZE
 // threads; returns the wave-uniform count. The list is written but not yet
 // visible: a workgroup that goes on (count > 0) synchronises before it reads.
+// IdT is the routing's element type: int64 expert ids (torch.topk), or the
+// int32 adapter slots of lora_batched.hip, where a pair is a token row.
+template <typename IdT>
 DEV_INLINE int build_pair_list(int (&list)[kMaxRows], int (&wave_hits)[kWaves],
-                               const int64_t* __restrict__ selected,
+                               const IdT* __restrict__ selected,
                                const int n_pairs, const int expert,
                                const int wave, const int lane) {
   const int p = threadIdx.x;
-  const bool hit = p < n_pairs && selected[p] == (int64_t)expert;
+  const bool hit = p < n_pairs && selected[p] == (IdT)expert;
   const unsigned long long hits = __ballot(hit);
   if (lane == 0) wave_hits[wave] = __popcll(hits);
   __syncthreads();

@@ -36,6 +36,9 @@ class ForwardBatch:
 
     # per-token LoRA adapter ids (None when no adapters are active)
     lora_ids: torch.Tensor | None = None  # int32 [T]
+    # the rows' adapter slots for the batched apply (LoRAManager.slot_of):
+    # 0 on base and pad rows and on rows whose adapter has no slot
+    lora_slots: torch.Tensor | None = None  # int32 [T]
 
     # multimodal splice: rows of mm_embeds replace the token embeddings at
     # packed positions mm_idx (image-placeholder tokens; models/vision.py)

@@ -5,7 +5,13 @@ per-token adapter ids (ForwardBatch.lora_ids); apply() computes
 
     y[tok] += B_a (A_a x[tok]) * (alpha / r)      for tok with adapter a
 
-grouped per adapter — the segmented-gather form of SGMV. Weight format:
+grouped per adapter — the segmented-gather form of SGMV. Decode-sized steps
+on GPU (T <= ops.lora_batched_t()) serve all adapters of the batch in two
+launches instead (ops.lora_apply, csrc/lora_batched.hip): every loaded
+adapter owns a slot, ForwardBatch.lora_slots carries the rows' slots, and one
+LoraTable per (target, layer) holds the slots' weight addresses on the device.
+Nothing on that path depends on which adapters a batch names, so the decode
+step is graph-captured with adapters loaded (runner.py). Weight format:
 HF PEFT safetensors when `path` exists; otherwise deterministic random-init
 (rank 16) for synthetic/benchmark use (no network for real checkpoints).
 
@@ -15,9 +21,73 @@ prefix blocks are never shared across adapters (kvcache.py).
 from __future__ import annotations
 
 import os
+import struct
 from typing import Optional
 
 import torch
+
+from kubeai_amd import ops
+
+
+class LoraTable:
+    """The adapters of one (target, layer) as ops.lora_apply takes them: `dev`,
+    an int64 [slots, 4] device tensor of (A address, B address, R, scale as
+    fp32 bits) per slot, `host`, its host copy (the launcher checks the rows
+    there, without a sync), and `rows`, the (A, B, scale) the addresses point
+    at. Slot 0 is "no adapter"; R == 0 is "nothing to add".
+
+    `dev` is allocated once: set_row and clear_row rewrite it in place, in
+    stream order, so a captured graph that reads it stays valid."""
+
+    SLOTS = 16  # slot 0 plus 15 adapters: the slot dimension of both grids
+    MAX_RANK = 64
+
+    def __init__(self, K: int, N: int, device, slots: int = SLOTS):
+        self.K, self.N = K, N
+        self.host = torch.zeros(slots, 4, dtype=torch.int64)
+        self.dev = torch.zeros(slots, 4, dtype=torch.int64, device=device)
+        self.rows: list = [None] * slots
+
+    def set_row(self, slot: int, A: torch.Tensor, B: torch.Tensor, scale: float):
+        """A [R, K], B [N, R], bf16, contiguous, R % 8 == 0, R <= 64."""
+        if not 1 <= slot < len(self.rows):
+            raise RuntimeError(f"lora table: slot {slot} outside [1, {len(self.rows)})")
+        if self.K % 8 or self.N % 16:
+            raise RuntimeError(
+                f"lora table: K {self.K} and N {self.N}, need multiples of 8 and 16"
+            )
+        R = A.shape[0]
+        if R % 8 or not 0 < R <= self.MAX_RANK:
+            raise RuntimeError(
+                f"lora table: rank {R}, need a multiple of 8 up to {self.MAX_RANK}"
+            )
+        if tuple(A.shape) != (R, self.K) or tuple(B.shape) != (self.N, R):
+            raise RuntimeError(
+                f"lora table: A {list(A.shape)} and B {list(B.shape)}, need "
+                f"[{R}, {self.K}] and [{self.N}, {R}]"
+            )
+        for w in (A, B):
+            if (
+                w.dtype != torch.bfloat16 or w.device != self.dev.device
+                or not w.is_contiguous() or w.data_ptr() % 16
+            ):
+                raise RuntimeError(
+                    "lora table: A and B must be contiguous bf16 on the "
+                    "table's device, 16-byte aligned"
+                )
+        packed = struct.pack("<f", scale)
+        self.host[slot] = torch.tensor(
+            [A.data_ptr(), B.data_ptr(), R, struct.unpack("<I", packed)[0]],
+            dtype=torch.int64,
+        )
+        self.dev[slot].copy_(self.host[slot])
+        self.rows[slot] = (A, B, struct.unpack("<f", packed)[0])
+
+    def clear_row(self, slot: int) -> None:
+        """R = 0 on the device first; the tensors are released after it."""
+        self.host[slot] = 0
+        self.dev[slot].copy_(self.host[slot])
+        self.rows[slot] = None
 
 
 class LoRAManager:
@@ -30,6 +100,13 @@ class LoRAManager:
         self.dtype = dtype
         # adapters[lora_id][target] = list over layers of (A [r,in], B [out,r], scale)
         self.adapters: dict[int, dict[str, list[tuple[torch.Tensor, torch.Tensor, float]]]] = {}
+        # batched path: lora_id -> slot, the ids whose ranks it cannot take,
+        # tables[target][layer] (built at the first load) and the K-split
+        # workspace all applies share
+        self.slots: dict[int, int] = {}
+        self._unbatchable: set[int] = set()
+        self.tables: dict[str, list[LoraTable]] | None = None
+        self.vpart: torch.Tensor | None = None
         model.lora_manager = self
         for m in model.modules():
             if hasattr(m, "qkv_proj"):  # Attention modules
@@ -46,9 +123,65 @@ class LoRAManager:
             self.adapters[lora_id] = self._load_peft(path)
         else:
             self.adapters[lora_id] = self._random_adapter(lora_id)
+        self._assign_slot(lora_id)
 
     def unload(self, lora_id: int) -> None:
+        slot = self.slots.pop(lora_id, None)
+        if slot is not None:
+            for tables in self.tables.values():
+                for table in tables:
+                    table.clear_row(slot)
+        self._unbatchable.discard(lora_id)
         self.adapters.pop(lora_id, None)
+
+    def slot_of(self, lora_id: int) -> Optional[int]:
+        return self.slots.get(lora_id)
+
+    def _assign_slot(self, lora_id: int) -> None:
+        """The lowest free slot, and the adapter's rows in every table. An
+        adapter stays without a slot when none is free or when one of its
+        ranks is not a multiple of 8 up to 64: steps then keep the sgmv loop."""
+        adapter = self.adapters[lora_id]
+        if self.tables is None:
+            self.tables = {
+                tgt: [
+                    LoraTable(A.shape[1], B.shape[0], self.device)
+                    for A, B, _ in layers
+                ]
+                for tgt, layers in adapter.items()
+            }
+            if torch.device(self.device).type == "cuda":
+                self.vpart = ops.lora_vpart(self.device)
+        # placeholders of missing targets (scale 0) are R = 0 rows
+        live = [
+            (tgt, layer, row)
+            for tgt, layers in adapter.items()
+            for layer, row in enumerate(layers)
+            if row[2] != 0.0
+        ]
+        free = set(range(1, LoraTable.SLOTS)) - set(self.slots.values())
+        if not free:
+            return
+        slot = min(free)
+        try:
+            for tgt, layer, (A, B, scale) in live:
+                self.tables[tgt][layer].set_row(slot, A, B, scale)
+        except RuntimeError:  # a rank or layout the batched kernels do not take
+            for tables in self.tables.values():
+                for table in tables:
+                    table.clear_row(slot)
+            self._unbatchable.add(lora_id)
+            return
+        self.slots[lora_id] = slot
+
+    def batched(self, T: int, on_gpu: bool) -> bool:
+        """Whether apply serves a step of T rows with ops.lora_apply."""
+        return (
+            on_gpu
+            and 1 <= T <= ops.lora_batched_t()
+            and not self._unbatchable
+            and len(self.slots) == len(self.adapters)
+        )
 
     @property
     def active(self) -> bool:
@@ -189,9 +322,17 @@ class LoRAManager:
         x: torch.Tensor,  # [T, in]
         y: torch.Tensor,  # [T, out] += delta (in-place)
         lora_ids: torch.Tensor,  # [T] int32
+        lora_slots: Optional[torch.Tensor] = None,  # [T] int32
     ) -> None:
-        """Segmented LoRA matmul: per-adapter token groups; one hand-written
-        SGMV kernel launch per adapter on GPU (csrc/sgmv.hip)."""
+        """Decode-sized steps on GPU: ops.lora_apply over the rows' slots, two
+        launches for all adapters and no sync. Otherwise the segmented LoRA
+        matmul: per-adapter token groups; one hand-written SGMV kernel launch
+        per adapter on GPU (csrc/sgmv.hip)."""
+        if lora_slots is not None and self.batched(x.shape[0], x.is_cuda):
+            ops.lora_apply(
+                y, x, lora_slots, self.tables[target][layer_idx], self.vpart
+            )
+            return
         present = torch.unique(lora_ids)
         for lid_t in present:
             lid = int(lid_t)

@@ -33,7 +33,12 @@ class _DecodeGraph:
 
     The five inputs are views of ONE int32 device buffer (the int64 slots
     first, for alignment), mirrored by a pinned host buffer: a step pads on
-    the host and uploads once. The captured addresses never change.
+    the host and uploads once. The captured addresses never change. A graph
+    captured with adapters loaded (lora=True) has the rows' adapter slots as a
+    sixth input at the end of the same buffer, and applies the adapters with
+    the batched kernels (ops.lora_apply), which read the slots and the
+    manager's tables on the device: loading, unloading and routing change
+    what a replay computes, never what it launches.
     KUBEAI_GRAPH_STAGED_INPUTS=0 uploads each input by itself from pageable
     memory and pads with device fills instead (for A/B runs).
     """
@@ -50,7 +55,8 @@ class _DecodeGraph:
             buf[4 * n : 5 * n],
         )
 
-    def __init__(self, runner: "ModelRunner", b_pad: int, bt_max: int):
+    def __init__(self, runner: "ModelRunner", b_pad: int, bt_max: int,
+                 lora: bool = False):
         import numpy as np
 
         dev = runner.device
@@ -58,15 +64,21 @@ class _DecodeGraph:
         self.bt_max = bt_max
         self.staged = os.environ.get("KUBEAI_GRAPH_STAGED_INPUTS", "1") != "0"
         words = b_pad * (5 + bt_max)
-        self._host = torch.zeros(words, dtype=torch.int32, pin_memory=True)
-        self._host_views = self._carve(self._host.numpy(), b_pad, bt_max, np.int64)
+        self._host = torch.zeros(
+            words + (b_pad if lora else 0), dtype=torch.int32, pin_memory=True
+        )
+        self._host_views = self._carve(
+            self._host.numpy()[:words], b_pad, bt_max, np.int64
+        )
+        self._host_lora = self._host.numpy()[words:]  # all 0: base rows
         self._host_views[2][:] = -1  # slots: nothing is cached
         self._host_views[4][:] = 1  # seq_lens
         self._dev = self._host.to(dev)
         (
             self.input_ids, self.positions, self.slots, self.block_tables,
             self.seq_lens,
-        ) = self._carve(self._dev, b_pad, bt_max, torch.int64)
+        ) = self._carve(self._dev[:words], b_pad, bt_max, torch.int64)
+        self.lora_slots = self._dev[words:] if lora else None
         logits_idx = torch.arange(b_pad, dtype=torch.int64, device=dev)
         self.fb = ForwardBatch(
             input_ids=self.input_ids,
@@ -80,6 +92,10 @@ class _DecodeGraph:
             prefill_seq_lens=None,
             prefill_block_tables=None,
             logits_indices=logits_idx,
+            # lora_ids only tells the layers that adapters are live: the
+            # batched apply reads lora_slots
+            lora_ids=self.lora_slots,
+            lora_slots=self.lora_slots,
         )
         # Every row of a decode step is sampled, so a model that has
         # forward_logits runs the head on the hidden rows as they are (final
@@ -103,12 +119,21 @@ class _DecodeGraph:
         with torch.cuda.graph(self.graph):
             self.logits = step_logits()
 
-    def run(self, input_ids, positions, slots, tables, seq_lens) -> torch.Tensor:
+    def run(self, input_ids, positions, slots, tables, seq_lens,
+            lora_slots=None) -> torch.Tensor:
         """Lists of b ints and an int32 numpy table [b, <= bt_max]. Rows past
-        b are pad rows: slot -1, seq_len 1, block 0."""
+        b are pad rows: slot -1, seq_len 1, block 0, adapter slot 0.
+        lora_slots: the b rows' adapter slots, for a graph with lora=True."""
         b = len(input_ids)
         if not self.staged:
+            if self.lora_slots is not None:
+                self.lora_slots.zero_()
+                self.lora_slots[:b].copy_(
+                    torch.tensor(lora_slots, dtype=torch.int32), non_blocking=True
+                )
             return self._run_unstaged(input_ids, positions, slots, tables, seq_lens)
+        if self.lora_slots is not None:
+            self._host_lora[:b], self._host_lora[b:] = lora_slots, 0
         # The staging buffer is rewritten every step: the upload of the step
         # before has completed, every step ends in a device-to-host copy of
         # its samples (ModelRunner.execute).
@@ -179,7 +204,8 @@ class ModelRunner:
             and os.environ.get("KUBEAI_GRAPHS", "1") == "1"
             and (tp_group is None or os.environ.get("KUBEAI_TP_GRAPHS", "1") == "1")
         )
-        self._graphs: dict[int, _DecodeGraph] = {}
+        # b_pad -> graph; ("lora", b_pad) -> graph captured with adapters loaded
+        self._graphs: dict = {}
         # JSON-mode constrained decoding: per-request prefix automata +
         # a tokenizer the server/worker injects after startup
         self.tokenizer = None
@@ -398,10 +424,14 @@ class ModelRunner:
                 logit_idx.append(nd + qsl[j + 1] - 1)
 
         lora_ids = None
+        lora_slots: list[int] | None = None
         if getattr(self, "lora_manager", None) is not None and self.lora_manager.active:
             ids: list[int] = []
+            lora_slots = []
             for ss in out.all_seqs:
                 ids.extend([ss.req.lora_id] * ss.chunk_len)
+                slot = self.lora_manager.slot_of(ss.req.lora_id) or 0
+                lora_slots.extend([slot] * ss.chunk_len)
             lora_ids = torch.tensor(ids, dtype=torch.int32, device=self.device)
 
         # ---- pad the token stream to a bucket size --------------------
@@ -429,6 +459,7 @@ class ModelRunner:
                 lora_ids = torch.cat(
                     [lora_ids, torch.zeros(pad, dtype=torch.int32, device=self.device)]
                 )
+                lora_slots.extend([0] * pad)
 
         dev = self.device
         t32 = lambda x: torch.tensor(x, dtype=torch.int32, device=dev)
@@ -441,6 +472,7 @@ class ModelRunner:
             ),
             mm_embeds=torch.cat(mm_rows).to(dev) if mm_rows else None,
             lora_ids=lora_ids,
+            lora_slots=t32(lora_slots) if lora_slots is not None else None,
             input_ids=t32(input_ids),
             positions=t32(positions),
             slot_mapping=torch.tensor(slots, dtype=torch.int64, device=dev),
@@ -459,16 +491,19 @@ class ModelRunner:
         return table + [0] * (n - len(table))
 
     # ------------------------------------------------------------------
-    def _execute_graph(self, out: SchedulerOutput):
-        """Pure-decode step through a captured hipGraph (bucketed batch)."""
+    def _execute_graph(self, out: SchedulerOutput, lora: bool = False):
+        """Pure-decode step through a captured hipGraph (bucketed batch).
+        lora: adapters are loaded and the step takes the batched apply; such
+        graphs are kept apart from the ones captured without adapters."""
         b = len(out.decode)
         b_pad = _bucket(b)
         bt_max = (self.max_model_len + self.block_size - 1) // self.block_size
-        g = self._graphs.get(b_pad)
+        key = ("lora", b_pad) if lora else b_pad
+        g = self._graphs.get(key)
         if g is None:
             ok = True
             try:
-                g = _DecodeGraph(self, b_pad, bt_max)
+                g = _DecodeGraph(self, b_pad, bt_max, lora=lora)
             except Exception:
                 import traceback
 
@@ -490,7 +525,7 @@ class ModelRunner:
             if not ok:
                 self.enable_graphs = False
                 return None
-            self._graphs[b_pad] = g
+            self._graphs[key] = g
         bs = self.block_size
         ids, pos, slots, lens = [], [], [], []
         import numpy as np
@@ -505,6 +540,12 @@ class ModelRunner:
             lens.append(t + 1)
             bt = req.block_table
             tables[i, : len(bt)] = bt
+        if lora:
+            lm = self.lora_manager
+            return g.run(
+                ids, pos, slots, tables, lens,
+                [lm.slot_of(ss.req.lora_id) or 0 for ss in out.decode],
+            )
         return g.run(ids, pos, slots, tables, lens)
 
     @torch.inference_mode()
@@ -532,16 +573,17 @@ class ModelRunner:
             for r in sample_reqs
         ) or self.device.type != "cuda"  # the CPU references compute as given
         logits = None
+        lm = getattr(self, "lora_manager", None)
+        lora = lm is not None and lm.active
         if (
             self.enable_graphs
             and not out.prefill
             and out.decode
-            and not (
-                getattr(self, "lora_manager", None) is not None
-                and self.lora_manager.active
-            )
+            # adapters loaded: only the batched apply captures (no sync, no
+            # dynamic shape); a step it does not take runs eagerly
+            and (not lora or lm.batched(_bucket(len(out.decode)), True))
         ):
-            logits = self._execute_graph(out)
+            logits = self._execute_graph(out, lora)
         if logits is None:
             fb = self.build_batch(out)
             hidden = self.model(fb)  # [T, H]

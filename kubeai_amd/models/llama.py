@@ -183,7 +183,9 @@ class Attention(nn.Module):
             qkv = self.qkv_proj(x)
             lm = getattr(self, "_lora_manager", None)
             if lm is not None and lm.active and fb.lora_ids is not None:
-                lm.apply(self.layer_idx, "qkv", x, qkv, fb.lora_ids)
+                lm.apply(
+                    self.layer_idx, "qkv", x, qkv, fb.lora_ids, fb.lora_slots
+                )
         q, k, v = qkv.split(
             [self.n_q * self.hd, self.n_kv * self.hd, self.n_kv * self.hd], dim=-1
         )
@@ -212,7 +214,9 @@ class Attention(nn.Module):
     def _o_proj_bf16(self, attn_flat, fb: ForwardBatch, lm) -> torch.Tensor:
         result = self.o_proj(attn_flat)
         if lm is not None and lm.active and fb.lora_ids is not None:
-            lm.apply(self.layer_idx, "o", attn_flat, result, fb.lora_ids)
+            lm.apply(
+                self.layer_idx, "o", attn_flat, result, fb.lora_ids, fb.lora_slots
+            )
         return result
 
 
@@ -240,11 +244,15 @@ class MLP(nn.Module):
             and fb.lora_ids is not None and self.layer_idx is not None
         )
         if lora_live:
-            lm.apply(self.layer_idx, "gate_up", x, h, fb.lora_ids)
+            lm.apply(
+                self.layer_idx, "gate_up", x, h, fb.lora_ids, fb.lora_slots
+            )
         a = ops.gelu_and_mul(h) if self.gelu else ops.silu_and_mul(h)
         y = self.down_proj(a)
         if lora_live:
-            lm.apply(self.layer_idx, "down", a, y, fb.lora_ids)
+            lm.apply(
+                self.layer_idx, "down", a, y, fb.lora_ids, fb.lora_slots
+            )
         return y
 
 

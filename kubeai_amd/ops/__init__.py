@@ -460,6 +460,47 @@ def fp8_moe_mlp(x, selected, weights, gate_up_group, down_group):
     return moe_combine(y, selected, weights, gate_up_group.E)
 
 
+# ---------------- batched multi-LoRA apply, routed on the device ------------
+# `table` below is an engine.lora.LoraTable: the device table of one (target,
+# layer)'s adapter addresses, its host copy and the tensors it points at.
+
+
+def lora_batched_t() -> int:
+    """Largest T for which LoRAManager.apply takes lora_apply:
+    KUBEAI_LORA_BATCHED_T, 64 when unset, at most 64; 0 keeps the per-adapter
+    sgmv loop (and with it eager decode) at every T. Read at call time: the
+    tests and A/B runs flip it."""
+    try:
+        limit = int(os.environ.get("KUBEAI_LORA_BATCHED_T", "64"))
+    except ValueError:
+        return 64
+    return max(0, min(limit, 64))
+
+
+def lora_vpart(device, T: int = 64) -> torch.Tensor:
+    """Workspace one lora_apply needs at most: fp32 [32 splits, T, 64]."""
+    return torch.empty(32 * T * 64, dtype=torch.float32, device=device)
+
+
+def lora_apply(y, x, slots, table, vpart=None, ks: int = 0) -> None:
+    """In place, for every row t with s = slots[t] >= 1 and rank R_s > 0:
+    y[t] = bf16(float(y[t]) + B_s vb[t]), vb[t] = bf16(scale_s * A_s x[t]).
+    All adapters of the batch in two launches on GPU; rows of slot 0 and of
+    empty slots are never written. slots is int32 [T], T <= 64, x [T, K] with
+    K % 8 == 0, y [T, N] with N % 16 == 0, ranks multiples of 8 up to 64.
+    vpart (lora_vpart) must be passed where nothing may be allocated, as under
+    graph capture; ks overrides the K split of _C.lora_plan."""
+    if not x.is_cuda:
+        ref.lora_apply(y, x, slots, table.rows)
+        return
+    _require_ext()
+    if x.dim() == 2 and (x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16):
+        x = x.contiguous()
+    if vpart is None:
+        vpart = lora_vpart(x.device, x.shape[0])
+    _C.lora_apply(y, x, slots, table.dev, table.host, vpart, ks)
+
+
 def _empty_fp8_rows(shape, device):
     """Uninitialised (e4m3 `shape`, f32 [shape[0]] row scales) for an fp8
     producer to fill."""

@@ -347,6 +347,23 @@ def moe_mlp(x, selected, weights, gate_up_weights, down_weights):
     return moe_combine(y, selected, weights, len(gate_up_weights))
 
 
+def lora_apply(y, x, slots, rows) -> None:
+    """In place: y[t] = bf16(float(y[t]) + B_s vb[t]) with vb[t] =
+    bf16(scale_s * A_s x[t]) for s = slots[t]; rows[s] is (A [R, K], B [N, R],
+    scale) or None. The batched kernel's two roundings (csrc/lora_batched.hip)
+    with fp32 sums; rows of slot 0 or of a slot without adapter are untouched."""
+    for s, row in enumerate(rows):
+        if s == 0 or row is None:
+            continue
+        A, B, scale = row
+        idx = (slots == s).nonzero(as_tuple=True)[0]
+        if idx.numel() == 0:
+            continue
+        v = x[idx].float() @ A.float().T
+        vb = (v * torch.tensor(scale, dtype=torch.float32)).to(torch.bfloat16)
+        y[idx] = (y[idx].float() + vb.float() @ B.float().T).to(torch.bfloat16)
+
+
 # ---------------------------------------------------------------------------
 # sampling
 # ---------------------------------------------------------------------------
