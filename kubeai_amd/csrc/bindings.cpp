@@ -79,6 +79,13 @@ void gumbel_sample_logprob(torch::Tensor out, torch::Tensor out_logprob,
                            int64_t step);
 void token_logprobs(torch::Tensor out_logprob, torch::Tensor out_lse,
                     torch::Tensor logits, torch::Tensor tokens);
+// a decode step's inputs become the next step's, on the device
+// (decode_advance.hip)
+void decode_advance(torch::Tensor input_ids, torch::Tensor positions,
+                    torch::Tensor slots, torch::Tensor seq_lens,
+                    torch::Tensor block_tables, torch::Tensor n_blocks,
+                    torch::Tensor b_live, torch::Tensor tokens,
+                    int64_t block_size);
 void sgmv(torch::Tensor y, torch::Tensor x, torch::Tensor A, torch::Tensor B,
           torch::Tensor idx, double scale);
 // batched multi-LoRA apply routed on the device (lora_batched.hip); table is
@@ -211,6 +218,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "temperature sampling + the token's logprob and the row logsumexp");
   m.def("token_logprobs", &token_logprobs,
         "logprob of given tokens and the row logsumexp, one launch");
+  m.def("decode_advance", &decode_advance,
+        "in place: a pure-decode step's ids, positions, slots and seq_lens "
+        "become the next step's, from the sampled tokens and the block tables");
   m.def("rmsnorm_fp8", &rmsnorm_fp8, "rmsnorm with fused fp8 row quant");
   m.def("fused_add_rmsnorm_fp8", &fused_add_rmsnorm_fp8,
         "residual add + rmsnorm with fused fp8 row quant");

@@ -15,7 +15,7 @@ import torch
 from kubeai_amd.models.config import ModelArchConfig, PRESETS
 
 from .kvcache import BlockManager
-from .runner import ModelRunner
+from .runner import ModelRunner, self_feed_ok
 from .scheduler import Request, SamplingParams, Scheduler
 
 
@@ -175,7 +175,61 @@ class LLMEngine:
         return self.scheduler.has_work()
 
     # ------------------------------------------------------------------
+    def _predict_run_ahead(self, out) -> bool:
+        """Will the step after `out` be `out`'s decode batch again, whatever
+        tokens `out` samples (a stop token aside)? If so, grow the block
+        tables for it and tell the runner to enqueue that step's replay
+        before it waits for this step's tokens. The host then does this
+        step's bookkeeping while the device runs the next one; the next
+        step() adopts the replay if the scheduler decides as predicted, and
+        lets it finish unused if not (runner.runahead_stats)."""
+        runner, sched = self.runner, self.scheduler
+        if (
+            not runner.self_feed
+            or out.prefill
+            or out.preempted
+            or not out.decode
+            or len(out.decode) != len(sched.running)
+            or sched._aborted
+        ):
+            return False
+        lm = getattr(runner, "lora_manager", None)
+        if lm is not None and lm.active:
+            return False
+        reqs = [ss.req for ss in out.decode]
+        for r in reqs:
+            if not self_feed_ok(r.params):
+                return False
+            # ends by length in this step: the batch changes
+            if (
+                r.num_generated + 1 >= r.params.max_tokens
+                or len(r.tokens) + 1 >= sched.max_model_len
+            ):
+                return False
+        next_defers = (
+            sched.prefill_interval > 1
+            and (sched._step_idx + 1) % sched.prefill_interval != 0
+        )
+        if sched.waiting and not next_defers:
+            return False  # the next step admits a prefill
+        # The replay ahead writes the cache row of position num_computed + 1
+        # of each request and reads the rows before it: it touches only
+        # blocks the batch owns. A request at a block boundary gets the next
+        # block now, the one the scheduler would append one step later; if
+        # the pool cannot give it without preempting, nothing runs ahead.
+        # ModelRunner._run_ahead asserts this before it enqueues.
+        bs = self.cfg.block_size
+        grow = [r for r in reqs if len(r.block_table) * bs < r.num_computed + 2]
+        if len(grow) > self.block_manager.num_free_blocks:
+            return False
+        for r in grow:
+            self.block_manager.append_block(r.block_table)
+        return True
+
     def step(self) -> list[RequestOutput]:
+        if self.scheduler._aborted:
+            # an abort frees blocks the replay ahead may still write to
+            self.runner.wait_inflight()
         out = self.scheduler.schedule()
         results: list[RequestOutput] = []
         for req in out.rejected:
@@ -191,11 +245,24 @@ class LLMEngine:
                 )
             )
         if out.is_empty:
+            self.runner.drop_inflight()
             return results
-        sampled = self.runner.execute(out, self.step_count)
+        sampled = self.runner.execute(
+            out, self.step_count, run_ahead=self._predict_run_ahead(out)
+        )
         self.step_count += 1
         now = time.monotonic()
-        finished = self.scheduler.finish_step(out, sampled, now)
+        # A request that ends here on a stop token is still a row of the
+        # replay enqueued ahead, which writes one more cache row into the
+        # request's last block: the blocks go back only once it has run.
+        held: Optional[list] = [] if self.runner._inflight is not None else None
+        finished = self.scheduler.finish_step(out, sampled, now, defer_free=held)
+        if held:
+            self.runner.wait_inflight()
+            for table in held:
+                self.block_manager.free(table)
+            if not self.scheduler.running:
+                self.runner.drop_inflight()  # no step will come for it
         finished_ids = {r.request_id for r in finished}
         for rid in finished_ids:
             self.runner.release_request(rid)
@@ -289,4 +356,9 @@ class LLMEngine:
             "kv_usage": self.block_manager.usage(),
             "prefix_cache_hit_rate": self.block_manager.hit_rate(),
             "step_count": self.step_count,
+            # decode run-ahead: replays enqueued before the step's tokens
+            # were read, and what became of them at the next step
+            "runahead_enqueued": self.runner.runahead_stats["enqueued"],
+            "runahead_adopted": self.runner.runahead_stats["adopted"],
+            "runahead_discarded": self.runner.runahead_stats["discarded"],
         }

@@ -41,6 +41,23 @@ class _DecodeGraph:
     what a replay computes, never what it launches.
     KUBEAI_GRAPH_STAGED_INPUTS=0 uploads each input by itself from pageable
     memory and pads with device fills instead (for A/B runs).
+
+    A self-feeding graph (self_feed=True; never with adapters) also holds the
+    greedy sampler over the bf16 logits, writing into buffers it keeps, and
+    begins with ops.decode_advance, which turns the inputs the replay before
+    left behind into this replay's on the device: the token sampled there at
+    the next position, its slot from the row's block table. Two more inputs
+    follow the tables in the buffer, n_blocks [b_pad] and b_live [1]: an
+    uploaded step has b_live 0 and runs as uploaded, a replay enqueued ahead
+    has the number of requests there. (The advance stands first, not last:
+    as the last node it would need the block of the step after next, one
+    step before the scheduler appends it.) Such a graph can be replayed again
+    before the host has seen the step's tokens (ModelRunner._run_ahead);
+    between two replays only b_live and the table rows that gain a block are
+    uploaded, from a second staging buffer, so that no buffer is rewritten
+    while an upload from it may still be in flight. On a
+    CPU device nothing is captured: the same steps run eagerly through the
+    reference ops, which is how the engine logic is tested without a GPU.
     """
 
     @staticmethod
@@ -56,16 +73,22 @@ class _DecodeGraph:
         )
 
     def __init__(self, runner: "ModelRunner", b_pad: int, bt_max: int,
-                 lora: bool = False):
+                 lora: bool = False, self_feed: bool = False):
         import numpy as np
 
+        assert not (lora and self_feed)
         dev = runner.device
+        cuda = dev.type == "cuda"
         self.b_pad = b_pad
         self.bt_max = bt_max
-        self.staged = os.environ.get("KUBEAI_GRAPH_STAGED_INPUTS", "1") != "0"
+        self.self_feed = self_feed
+        self.staged = (
+            os.environ.get("KUBEAI_GRAPH_STAGED_INPUTS", "1") != "0" or self_feed
+        )
         words = b_pad * (5 + bt_max)
+        extra = b_pad if lora else (b_pad + 1 if self_feed else 0)
         self._host = torch.zeros(
-            words + (b_pad if lora else 0), dtype=torch.int32, pin_memory=True
+            words + extra, dtype=torch.int32, pin_memory=cuda
         )
         self._host_views = self._carve(
             self._host.numpy()[:words], b_pad, bt_max, np.int64
@@ -73,7 +96,19 @@ class _DecodeGraph:
         self._host_lora = self._host.numpy()[words:]  # all 0: base rows
         self._host_views[2][:] = -1  # slots: nothing is cached
         self._host_views[4][:] = 1  # seq_lens
-        self._dev = self._host.to(dev)
+        self._dev = self._host.to(dev) if cuda else self._host.clone()
+        if self_feed:
+            # the second staging buffer: the tail (tables, n_blocks, b_live)
+            # of the two takes turns (ModelRunner._run_ahead -> patch_tables)
+            self._tail = 5 * b_pad
+            self._host_alt = torch.zeros_like(self._host, pin_memory=cuda)
+            self.n_blocks = self._dev[words : words + b_pad]
+            self.b_live = self._dev[words + b_pad :]
+            self._samples_host = torch.zeros(
+                2 * b_pad, dtype=torch.int64, pin_memory=cuda
+            )
+            self._fetched = torch.cuda.Event() if cuda else None
+            self.sample = ops.empty_sample_result(b_pad, dev)
         (
             self.input_ids, self.positions, self.slots, self.block_tables,
             self.seq_lens,
@@ -105,11 +140,31 @@ class _DecodeGraph:
         fused_head = getattr(runner.model, "forward_logits", None)
 
         def step_logits():
+            if self_feed:
+                ops.decode_advance(
+                    self.input_ids, self.positions, self.slots, self.seq_lens,
+                    self.block_tables, self.n_blocks, self.b_live,
+                    self.sample.tokens, runner.block_size,
+                )
             if fused_head is not None:
-                return fused_head(self.fb, fp32=False)
-            h = runner.model(self.fb)
-            return runner.model.compute_logits(h[logits_idx])
+                # the CPU references compute as given: fp32 there
+                logits = fused_head(self.fb, fp32=not cuda)
+            else:
+                h = runner.model(self.fb)
+                logits = runner.model.compute_logits(h[logits_idx])
+            if self_feed:
+                # every row is sampled, pad rows too: rows are independent,
+                # and the sampler's grid then never changes between replays
+                ops.greedy_sample_logprob(logits.contiguous(), out=self.sample)
+            return logits
 
+        self.graph = None
+        if not cuda:
+            self._step = step_logits  # replayed eagerly
+            return
+        # (not kept on a GPU: the closure refers back to self, and a graph
+        # in a reference cycle outlives its engine until a collection, with
+        # its memory pool and its share of the capture RNG state)
         # warmup outside capture (allocator, hipBLASLt workspace)
         torch.cuda.synchronize()
         for _ in range(2):
@@ -119,11 +174,18 @@ class _DecodeGraph:
         with torch.cuda.graph(self.graph):
             self.logits = step_logits()
 
+    def replay(self) -> None:
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self.logits = self._step()
+
     def run(self, input_ids, positions, slots, tables, seq_lens,
-            lora_slots=None) -> torch.Tensor:
+            lora_slots=None, n_blocks=None) -> torch.Tensor:
         """Lists of b ints and an int32 numpy table [b, <= bt_max]. Rows past
         b are pad rows: slot -1, seq_len 1, block 0, adapter slot 0.
-        lora_slots: the b rows' adapter slots, for a graph with lora=True."""
+        lora_slots: the b rows' adapter slots, for a graph with lora=True.
+        n_blocks: the b rows' filled table entries, for a self-feeding graph."""
         b = len(input_ids)
         if not self.staged:
             if self.lora_slots is not None:
@@ -146,9 +208,68 @@ class _DecodeGraph:
         h_tables[:b, :w] = tables
         h_tables[:b, w:] = 0
         h_tables[b:] = 0
+        if self.self_feed:
+            h_tail = self._host.numpy()[5 * self.b_pad + h_tables.size :]
+            h_tail[:b] = n_blocks
+            h_tail[b : self.b_pad] = 0
+            h_tail[self.b_pad] = 0  # b_live: this step runs as uploaded
         self._dev.copy_(self._host, non_blocking=True)
-        self.graph.replay()
+        self.replay()
         return self.logits[:b]
+
+    # ---- self-feeding graphs only ------------------------------------
+    def patch_tables(self, b: int, grown: list) -> None:
+        """Before a replay enqueued ahead, over the b requests of the replay
+        before: b_live = b, and the rows that gained a block, as (row, index,
+        block id). The tail of the staging buffer that was NOT uploaded from
+        last takes the change, so the host never writes where a copy enqueued
+        one step ago may still be reading."""
+        t = self._tail
+        src, dst = self._host.numpy(), self._host_alt.numpy()
+        n_tab = self.b_pad * self.bt_max
+        # a row uploaded after the engine grew its table has the block already
+        grown = [g for g in grown if src[t + n_tab + g[0]] <= g[1]]
+        if not grown and src[-1] == b:
+            return
+        dst[t:] = src[t:]
+        tables = dst[t : t + n_tab].reshape(self.b_pad, self.bt_max)
+        nb = dst[t + n_tab :]
+        for row, i, bid in grown:
+            assert i == nb[row] and i < self.bt_max
+            tables[row, i] = bid
+            nb[row] = i + 1
+        dst[-1] = b
+        self._dev[t:].copy_(self._host_alt[t:], non_blocking=True)
+        self._host, self._host_alt = self._host_alt, self._host
+        words = self.b_pad * (5 + self.bt_max)
+        import numpy as np
+
+        self._host_views = self._carve(
+            self._host.numpy()[:words], self.b_pad, self.bt_max, np.int64
+        )
+
+    def fetch_async(self) -> None:
+        """Enqueue the copy of the last replay's samples to the host; the
+        next replay may be enqueued behind it."""
+        if self._fetched is not None:
+            self._samples_host.copy_(self.sample.packed, non_blocking=True)
+            self._fetched.record()
+        else:  # eager: the next replay replaces self.sample at once
+            self._cpu_samples = (
+                self.sample.tokens.tolist(), self.sample.logprob.tolist()
+            )
+
+    def fetch_wait(self, rows: list) -> tuple[list[int], list[float]]:
+        """(tokens, logprobs) of `rows` from the copy fetch_async enqueued;
+        waits for that copy alone, not for the stream."""
+        if self._fetched is None:
+            tok, lp = self._cpu_samples
+        else:
+            self._fetched.synchronize()
+            n = self.b_pad
+            tok = self._samples_host[:n].tolist()
+            lp = self._samples_host[n:].view(torch.float32)[:n].tolist()
+        return [tok[r] for r in rows], [lp[r] for r in rows]
 
     def _run_unstaged(self, input_ids, positions, slots, tables, seq_lens):
         b = len(input_ids)
@@ -206,6 +327,21 @@ class ModelRunner:
         )
         # b_pad -> graph; ("lora", b_pad) -> graph captured with adapters loaded
         self._graphs: dict = {}
+        # Decode run-ahead: an all-greedy pure-decode step goes through a
+        # self-feeding graph (("feed", b_pad)), and the engine may have the
+        # next step's replay enqueued before this step's tokens are read
+        # (_run_ahead). KUBEAI_DECODE_RUNAHEAD=0: the sampler stays behind
+        # the graph and every step uploads its inputs. Not with tensor
+        # parallelism: the ranks would have to agree on every prediction.
+        self.self_feed = (
+            enable_graphs
+            and os.environ.get("KUBEAI_GRAPHS", "1") == "1"
+            and os.environ.get("KUBEAI_DECODE_RUNAHEAD", "1") != "0"
+            and (tp_group is None or getattr(tp_group, "world", 2) <= 1)
+            and (self.enable_graphs or self.device.type == "cpu")
+        )
+        self._inflight: Optional[dict] = None  # the replay enqueued ahead
+        self.runahead_stats = {"enqueued": 0, "adopted": 0, "discarded": 0}
         # JSON-mode constrained decoding: per-request prefix automata +
         # a tokenizer the server/worker injects after startup
         self.tokenizer = None
@@ -495,15 +631,31 @@ class ModelRunner:
         """Pure-decode step through a captured hipGraph (bucketed batch).
         lora: adapters are loaded and the step takes the batched apply; such
         graphs are kept apart from the ones captured without adapters."""
-        b = len(out.decode)
+        g = self._decode_graph(len(out.decode), lora=lora)
+        if g is None:
+            return None
+        ids, pos, slots, tables, lens = self._decode_inputs(out, g)
+        if lora:
+            lm = self.lora_manager
+            return g.run(
+                ids, pos, slots, tables, lens,
+                [lm.slot_of(ss.req.lora_id) or 0 for ss in out.decode],
+            )
+        return g.run(ids, pos, slots, tables, lens)
+
+    def _decode_graph(self, b: int, lora: bool = False, self_feed: bool = False):
+        """The graph for b decode rows, captured on first use; None (and no
+        more graphs) where capture fails."""
         b_pad = _bucket(b)
         bt_max = (self.max_model_len + self.block_size - 1) // self.block_size
-        key = ("lora", b_pad) if lora else b_pad
+        key = ("lora", b_pad) if lora else ("feed", b_pad) if self_feed else b_pad
         g = self._graphs.get(key)
         if g is None:
             ok = True
             try:
-                g = _DecodeGraph(self, b_pad, bt_max, lora=lora)
+                g = _DecodeGraph(
+                    self, b_pad, bt_max, lora=lora, self_feed=self_feed
+                )
             except Exception:
                 import traceback
 
@@ -524,13 +676,18 @@ class ModelRunner:
                 ok = ok and int(flag.item()) == 1
             if not ok:
                 self.enable_graphs = False
+                self.self_feed = False
                 return None
             self._graphs[key] = g
+        return g
+
+    def _decode_inputs(self, out: SchedulerOutput, g: _DecodeGraph):
+        """(ids, positions, slots, tables, seq_lens) of a pure-decode step."""
         bs = self.block_size
         ids, pos, slots, lens = [], [], [], []
         import numpy as np
 
-        tables = np.zeros((b, g.bt_max), dtype=np.int32)
+        tables = np.zeros((len(out.decode), g.bt_max), dtype=np.int32)
         for i, ss in enumerate(out.decode):
             req = ss.req
             t = ss.chunk_start
@@ -540,21 +697,129 @@ class ModelRunner:
             lens.append(t + 1)
             bt = req.block_table
             tables[i, : len(bt)] = bt
-        if lora:
-            lm = self.lora_manager
-            return g.run(
-                ids, pos, slots, tables, lens,
-                [lm.slot_of(ss.req.lora_id) or 0 for ss in out.decode],
+        return ids, pos, slots, tables, lens
+
+    # ------------------------------------------------------------------
+    # decode run-ahead
+    def drop_inflight(self) -> None:
+        """Let the replay enqueued ahead finish and forget its samples. What
+        it wrote to the cache are rows that the step computed in its place
+        writes again, with the same values."""
+        fl, self._inflight = self._inflight, None
+        if fl is None:
+            return
+        self.wait_inflight(fl)
+        self.runahead_stats["discarded"] += 1
+
+    def wait_inflight(self, fl: Optional[dict] = None) -> None:
+        """Block until the replay enqueued ahead has left the device."""
+        fl = fl or self._inflight
+        if fl is not None and fl["done"] is not None:
+            fl["done"].synchronize()
+
+    def _adoptable(self, fl: dict, out: SchedulerOutput) -> Optional[list]:
+        """The in-flight replay's rows for out.decode, if that replay computed
+        this very step: the same requests at the same positions in the same
+        order, less the ones that ended on a stop token meanwhile."""
+        rows = []
+        for ss in out.decode:
+            at = fl["rows"].get(ss.req.request_id)
+            if at is None or at[1] != ss.chunk_start:
+                return None
+            rows.append(at[0])
+        return rows if rows == sorted(rows) else None
+
+    def _run_ahead(self, g: _DecodeGraph, out: SchedulerOutput) -> None:
+        """Replay g once more, as the step after `out` over the same requests,
+        before `out`'s tokens have reached the host: the replay's first node,
+        decode_advance, makes that step's inputs on the device. The engine has grown the block
+        tables first (LLMEngine._predict_run_ahead)."""
+        bs = self.block_size
+        grown, rows = [], {}
+        for i, ss in enumerate(out.decode):
+            req, p = ss.req, ss.chunk_start + 1
+            # The replay writes position p of every row and nothing else:
+            # memory the batch owns, or it is not enqueued.
+            assert p // bs < len(req.block_table) <= g.bt_max, (
+                "run-ahead without a block for the next position"
             )
-        return g.run(ids, pos, slots, tables, lens)
+            assert p + 1 <= self.max_model_len
+            if p % bs == 0:
+                # the device copy of this row ended one entry earlier
+                grown.append((i, p // bs, req.block_table[p // bs]))
+            rows[req.request_id] = (i, p)
+        g.patch_tables(len(out.decode), grown)
+        g.replay()
+        done = None
+        if self.device.type == "cuda":
+            done = torch.cuda.Event()
+            done.record()
+        self._inflight = {"graph": g, "rows": rows, "done": done}
+        self.runahead_stats["enqueued"] += 1
+
+    def _execute_self_feed(self, out: SchedulerOutput, run_ahead: bool):
+        """An all-greedy pure-decode step through a self-feeding graph:
+        (tokens, logprobs), or None where no graph could be captured."""
+        fl, self._inflight = self._inflight, None
+        b = len(out.decode)
+        g = rows = None
+        if fl is not None:
+            rows = self._adoptable(fl, out)
+            if rows is None:
+                self._inflight = fl
+                self.drop_inflight()
+            else:
+                g = fl["graph"]
+                self.runahead_stats["adopted"] += 1
+        if rows is None:
+            g = self._decode_graph(b, self_feed=True)
+            if g is None:
+                return None
+            ids, pos, slots, tables, lens = self._decode_inputs(out, g)
+            g.run(
+                ids, pos, slots, tables, lens,
+                n_blocks=[len(ss.req.block_table) for ss in out.decode],
+            )
+            rows = list(range(b))
+        g.fetch_async()
+        # rows that ended meanwhile leave holes: the next step uploads afresh
+        if run_ahead and rows == list(range(b)):
+            self._run_ahead(g, out)
+        return g.fetch_wait(rows)
 
     @torch.inference_mode()
-    def execute(self, out: SchedulerOutput, step: int) -> dict[str, int]:
-        """Run one forward + sampling; returns request_id -> sampled token."""
+    def execute(
+        self, out: SchedulerOutput, step: int, run_ahead: bool = False
+    ) -> dict[str, int]:
+        """Run one forward + sampling; returns request_id -> sampled token.
+        run_ahead: the caller expects the next step to be this step's decode
+        batch again and has grown the block tables for it; a step that
+        qualifies then leaves that step's replay enqueued behind it."""
         # assemble sampling params in the same order as logits rows
         sample_reqs = [ss.req for ss in out.decode] + [
             ss.req for ss in out.prefill if ss.samples
         ]
+        lm = getattr(self, "lora_manager", None)
+        lora = lm is not None and lm.active
+        if (
+            self.self_feed
+            and out.decode
+            and not out.prefill
+            and not lora
+            and all(self_feed_ok(r.params) for r in sample_reqs)
+        ):
+            res = self._execute_self_feed(out, run_ahead)
+            if res is not None:
+                tokens, logprobs = res
+                self.last_logprobs = {
+                    r.request_id: float(lp)
+                    for r, lp in zip(sample_reqs, logprobs)
+                }
+                self.last_top_logprobs = {}
+                return {
+                    r.request_id: int(t) for r, t in zip(sample_reqs, tokens)
+                }
+        self.drop_inflight()
         # The samplers read bf16 logits with the results of logits.float();
         # whatever edits or re-reads logits in fp32 (penalties, logit_bias,
         # nucleus rejection, JSON mode, top alternatives) gets them widened.
@@ -573,8 +838,6 @@ class ModelRunner:
             for r in sample_reqs
         ) or self.device.type != "cuda"  # the CPU references compute as given
         logits = None
-        lm = getattr(self, "lora_manager", None)
-        lora = lm is not None and lm.active
         if (
             self.enable_graphs
             and not out.prefill
@@ -985,6 +1248,19 @@ def _bucket(n: int) -> int:
         if n <= b:
             return b
     return n
+
+
+def self_feed_ok(p) -> bool:
+    """May a request with these SamplingParams be sampled inside the decode
+    graph? Greedy, and nothing on the host edits or re-reads its logits."""
+    return (
+        p.temperature <= 0.0
+        and not p.presence_penalty
+        and not p.frequency_penalty
+        and not p.logit_bias
+        and not p.json_mode
+        and p.logprobs <= 0
+    )
 
 
 def _seed_of(request_id: str) -> int:

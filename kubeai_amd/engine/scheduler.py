@@ -349,13 +349,16 @@ class Scheduler:
 
     # ----------------------------------------------------------------
     def finish_step(
-        self, output: SchedulerOutput, sampled: dict[str, int], now: Optional[float] = None
+        self, output: SchedulerOutput, sampled: dict[str, int], now: Optional[float] = None,
+        defer_free: Optional[list] = None,
     ) -> list[Request]:
         """Commit a step: advance counters, append sampled tokens, seal
         full blocks into the prefix cache, finish/free requests.
 
         `sampled` maps request_id -> token for every seq with samples=True.
-        Returns requests that finished this step.
+        Returns requests that finished this step. With `defer_free` the
+        finished requests' block tables are appended to it instead of freed:
+        the caller frees them once nothing on the device writes to them.
         """
         if now is None:
             now = time.monotonic()
@@ -386,7 +389,10 @@ class Scheduler:
             if req.status.finished:
                 finished.append(req)
         for req in finished:
-            self.bm.free(req.block_table)
+            if defer_free is not None:
+                defer_free.append(req.block_table)
+            else:
+                self.bm.free(req.block_table)
             req.block_table = []
             self.running.remove(req)
         return finished

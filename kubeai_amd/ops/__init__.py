@@ -682,15 +682,29 @@ def sample_to_host(res: SampleResult) -> tuple[list[int], list[float]]:
     return host[:B].tolist(), host[B:].view(torch.float32)[:B].tolist()
 
 
-def greedy_sample_logprob(logits) -> SampleResult:
+def empty_sample_result(B: int, device) -> SampleResult:
+    """Buffers for greedy_sample_logprob(out=...): a decode graph keeps one
+    set, so that its first node can read the tokens of the replay before."""
+    packed = torch.zeros(2 * B, dtype=torch.int64, device=device)
+    f = packed[B:].view(torch.float32)
+    return SampleResult(packed[:B], f[:B], f[B:], packed)
+
+
+def greedy_sample_logprob(logits, out: SampleResult | None = None) -> SampleResult:
     """greedy_sample's token, plus its log-probability and the row's
-    logsumexp. On GPU the sampler's own two launches produce all three."""
+    logsumexp. On GPU the sampler's own two launches produce all three.
+    out: write into these buffers (empty_sample_result) and return them."""
     if logits.is_cuda:
         _require_ext()
-        res = _empty_sample_result(logits)
+        res = out if out is not None else _empty_sample_result(logits)
         _C.greedy_sample_logprob(res.tokens, res.logprob, res.lse, logits)
         return res
-    return SampleResult(*ref.greedy_sample_logprob(logits))
+    res = SampleResult(*ref.greedy_sample_logprob(logits))
+    if out is None:
+        return res
+    for dst, src in zip(out[:3], res[:3]):
+        dst.copy_(src)
+    return out
 
 
 def gumbel_sample_logprob(logits, temperature, seeds, step: int) -> SampleResult:
@@ -706,6 +720,22 @@ def gumbel_sample_logprob(logits, temperature, seeds, step: int) -> SampleResult
     return SampleResult(
         *ref.gumbel_sample_logprob(logits, temperature, seeds, step)
     )
+
+
+def decode_advance(input_ids, positions, slots, seq_lens, block_tables,
+                   n_blocks, b_live, tokens, block_size: int) -> None:
+    """In place: a pure-decode step's inputs become the next step's (the
+    sampled token at the next position and its slot from the block table),
+    for rows below b_live[0] whose next position has a block; every other row
+    stays as it is (ref.decode_advance). One launch, no host value read: the
+    last node of a self-feeding decode graph."""
+    if input_ids.is_cuda:
+        _require_ext()
+        _C.decode_advance(input_ids, positions, slots, seq_lens, block_tables,
+                          n_blocks, b_live, tokens, block_size)
+        return
+    ref.decode_advance(input_ids, positions, slots, seq_lens, block_tables,
+                       n_blocks, b_live, tokens, block_size)
 
 
 def token_logprobs(logits, tokens):

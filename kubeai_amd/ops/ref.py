@@ -454,6 +454,35 @@ def gumbel_sample_logprob(logits, temperature, seeds, step: int):
     return (tokens, *token_logprobs(logits, tokens))
 
 
+def decode_advance(
+    input_ids: torch.Tensor,     # [b_pad] int32, in place
+    positions: torch.Tensor,     # [b_pad] int32, in place
+    slots: torch.Tensor,         # [b_pad] int64, in place
+    seq_lens: torch.Tensor,      # [b_pad] int32, in place
+    block_tables: torch.Tensor,  # [b_pad, bt_max] int32
+    n_blocks: torch.Tensor,      # [b_pad] int32: filled entries of each row
+    b_live: torch.Tensor,        # [1] int32: rows below it are requests
+    tokens: torch.Tensor,        # [>= b_pad] int64: the rows' sampled tokens
+    block_size: int,
+) -> None:
+    """Turn the inputs of one pure-decode step into those of the next over the
+    same requests: the token just sampled at the next position, whose slot
+    follows from the row's block table. Pad rows (b >= b_live) keep their
+    values, and so does a row whose next position has no block yet
+    (p // block_size >= n_blocks[b]): it reads nothing past its table and a
+    replay computes its step again."""
+    b_pad, bt_max = block_tables.shape
+    for b in range(min(int(b_live[0]), b_pad)):
+        p = int(positions[b]) + 1
+        i = p // block_size
+        if i >= min(int(n_blocks[b]), bt_max):
+            continue
+        input_ids[b] = int(tokens[b])
+        positions[b] = p
+        seq_lens[b] += 1
+        slots[b] = int(block_tables[b, i]) * block_size + p % block_size
+
+
 def topk_topp_sample(
     logits: torch.Tensor,  # [B, V]
     temperature: torch.Tensor,  # [B]
