@@ -67,6 +67,13 @@ void fp8_moe_gemm(torch::Tensor y, torch::Tensor xq, torch::Tensor xs,
                   int64_t E, int64_t N, int64_t K, int64_t n_tiles);
 std::tuple<int64_t, int64_t> fp8_moe_plan(int64_t N, int64_t T, int64_t E,
                                           int64_t k);
+// W4A8 MXFP4 (mxfp4_gemm.hip); (qp, sp) is Mxfp4Weight's packed layout
+void mxfp4_dequant(torch::Tensor out, torch::Tensor qp, torch::Tensor sp,
+                   int64_t N, int64_t K);
+void mxfp4_gemm(torch::Tensor y, torch::Tensor xq, torch::Tensor xs,
+                torch::Tensor qp, torch::Tensor sp, int64_t N, int64_t K,
+                int64_t n_tiles);
+std::tuple<int64_t, int64_t> mxfp4_plan(int64_t M, int64_t N);
 void greedy_sample(torch::Tensor out, torch::Tensor logits);
 void gumbel_sample(torch::Tensor out, torch::Tensor logits,
                    torch::Tensor temperature, torch::Tensor seeds,
@@ -210,6 +217,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(16-row tiles, 16-column tiles per workgroup) fp8_moe_gemm launches "
         "with", pybind11::arg("N"), pybind11::arg("T"), pybind11::arg("E"),
         pybind11::arg("k"));
+  m.def("mxfp4_dequant", &mxfp4_dequant,
+        "packed MXFP4 weight -> bf16 [N, K], bit-equal to "
+        "Mxfp4Weight.dequant()");
+  m.def("mxfp4_gemm", &mxfp4_gemm,
+        "y = bf16((xq @ W^T) * xs) over a packed MXFP4 weight on the scaled "
+        "MFMA, e4m3 xq with fp32 row scales, M <= 64; n_tiles = 0 takes "
+        "mxfp4_plan's",
+        pybind11::arg("y"), pybind11::arg("xq"), pybind11::arg("xs"),
+        pybind11::arg("qp"), pybind11::arg("sp"), pybind11::arg("N"),
+        pybind11::arg("K"), pybind11::arg("n_tiles") = 0);
+  m.def("mxfp4_plan", &mxfp4_plan,
+        "(16-row tiles, 16-column tiles per workgroup) mxfp4_gemm launches "
+        "with", pybind11::arg("M"), pybind11::arg("N"));
   m.def("greedy_sample", &greedy_sample, "argmax sampling");
   m.def("gumbel_sample", &gumbel_sample, "temperature sampling (hash RNG)");
   m.def("greedy_sample_logprob", &greedy_sample_logprob,

@@ -39,6 +39,10 @@ class EngineConfig:
     # "int4" => W4A16 (quant_int4.py): AWQ-gemm checkpoints are served from
     #           their packed codes, float weights are quantized round-to-
     #           nearest (g=128); lm_head stays bf16; not with tensor parallelism
+    # "mxfp4" => W4A8 (quant_mxfp4.py): OCP microscaling FP4 weights, quantized
+    #           round-to-nearest; decode steps run on the scaled MFMA from the
+    #           fp8 producers' rows; lm_head stays bf16; dense models only, not
+    #           with tensor parallelism
     quantization: Optional[str] = None
     # "auto" = model dtype; "fp8_e5m2" halves KV bytes + doubles capacity
     kv_cache_dtype: str = "auto"

@@ -355,6 +355,15 @@ class ModelRunner:
                 "quantization='int4' is not implemented with tensor "
                 "parallelism"
             )
+        if quantization == "mxfp4" and (
+            tp_group is not None or arch.num_local_experts > 0
+        ):
+            # neither a sharding rule for the packed tensors nor a grouped
+            # expert kernel exists yet: reject loudly
+            raise NotImplementedError(
+                "quantization='mxfp4' is not implemented with tensor "
+                "parallelism or for MoE models"
+            )
         if tp_group is not None:
             from kubeai_amd.parallel.tp import TPLlamaForCausalLM
 
@@ -409,6 +418,13 @@ class ModelRunner:
             assert any(
                 isinstance(m, Int4Linear) for m in self.model.modules()
             ), "no linear layers converted to int4"
+        if quantization == "mxfp4":
+            # W4A8: the dense projections are quantized round-to-nearest
+            # onto e2m1 blocks; lm_head stays bf16
+            from .quant_mxfp4 import convert_to_mxfp4
+
+            n = convert_to_mxfp4(self.model)
+            assert n > 0, "no linear layers converted to mxfp4"
         if quantization == "fp8":
             # on CPU the Fp8Linear dequant fallback keeps the same
             # semantics (tests); the fast _scaled_mm path needs the GPU

@@ -1261,10 +1261,13 @@ def build_arg_parser() -> argparse.ArgumentParser:
     p.add_argument("--num-gpu-blocks", type=int, default=None)
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8_e5m2"],
                    default="auto")
-    p.add_argument("--quantization", choices=["fp8", "int4"], default=None,
+    p.add_argument("--quantization", choices=["fp8", "int4", "mxfp4"],
+                   default=None,
                    help="fp8 = W8A8 dynamic with fused activation quant; "
                         "int4 = W4A16, AWQ checkpoints served packed "
-                        "(float checkpoints are quantized round-to-nearest)")
+                        "(float checkpoints are quantized round-to-nearest); "
+                        "mxfp4 = W4A8, microscaling FP4 weights on the scaled "
+                        "MFMA (dense models, quantized round-to-nearest)")
     p.add_argument("--enable-lora", action="store_true")
     p.add_argument("--tensor-parallel-size", type=int, default=1)
     p.add_argument("--task", choices=["generate", "transcribe", "embed"],

@@ -291,6 +291,19 @@ def int4_reserve_workspace(device, numel: int) -> None:
         )
 
 
+def dequant_workspace(device, N: int, K: int):
+    """bf16 [N, K] view of the process-wide dequant workspace (the one
+    int4_reserve_workspace grows). Never allocates: a weight reserves its
+    size when it is built or moved."""
+    ws = _INT4_WORKSPACE.get(torch.device(device))
+    if ws is None or ws.numel() < N * K:
+        raise RuntimeError(
+            f"dequant workspace was not reserved for a [{N}, {K}] weight "
+            f"on {device}"
+        )
+    return ws[: N * K].view(N, K)
+
+
 def int4_dequant(w, out=None):
     """Packed int4 weight -> bf16 [N, K], bit-identical to w.dequant()."""
     if not w.qp.is_cuda:
@@ -321,14 +334,46 @@ def int4_linear(x, w):
         y = torch.empty((M, w.N), dtype=torch.bfloat16, device=x.device)
         _C.int4_gemm(y, x, w.qp, w.sp, w.zp, w.N, w.K, w.group)
         return y
-    ws = _INT4_WORKSPACE.get(x.device)
-    if ws is None or ws.numel() < w.N * w.K:
-        raise RuntimeError(
-            "int4 workspace was not reserved for this weight "
-            f"([{w.N}, {w.K}] on {x.device})"
-        )
-    dense = int4_dequant(w, out=ws[: w.N * w.K].view(w.N, w.K))
+    dense = int4_dequant(w, out=dequant_workspace(x.device, w.N, w.K))
     return torch.nn.functional.linear(x, dense)
+
+
+# ---------------- MXFP4 (W4A8, OCP microscaling FP4 weights) ----------------
+# `w` below is an engine.quant_mxfp4.Mxfp4Weight (packed qp/sp + N, K).
+
+# Largest M the scaled-MFMA kernel serves; above it Mxfp4Linear runs
+# mxfp4_dequant + the library GEMM and the decoder layers leave the fused
+# branch. See docs/kernels.md for how it is set.
+MXFP4_M_FUSED = 64
+
+
+def mxfp4_dequant(w, out=None):
+    """Packed MXFP4 weight -> bf16 [N, K], bit-identical to w.dequant()."""
+    if not w.qp.is_cuda:
+        res = w.dequant()
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+    _require_ext()
+    if out is None:
+        out = torch.empty((w.N, w.K), dtype=torch.bfloat16, device=w.qp.device)
+    _C.mxfp4_dequant(out, w.qp, w.sp, w.N, w.K)
+    return out
+
+
+def mxfp4_linear(xq, xs, w):
+    """y[m, n] = bf16(acc[m, n] * xs[m]), acc the fp32 sum over k of the exact
+    products xq[m, k] * w.dequant()[n, k]: bf16 [M, N]. xq is e4m3 [M, K] with
+    16-byte aligned rows, xs its fp32 row scales [M] or [M, 1], 1 <= M <= 64.
+    One launch on GPU, and a row's bytes do not depend on the rows around it."""
+    if not xq.is_cuda:
+        acc = xq.float() @ w.dequant().float().t()
+        return (acc * xs.reshape(-1, 1).float()).to(torch.bfloat16)
+    _require_ext()
+    y = torch.empty((xq.shape[0], w.N), dtype=torch.bfloat16, device=xq.device)
+    _C.mxfp4_gemm(y, xq, xs, w.qp, w.sp, w.N, w.K)
+    return y
 
 
 # ---------------- int4 MoE: grouped expert GEMMs, routed on the device ------
