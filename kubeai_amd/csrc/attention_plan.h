@@ -1,8 +1,9 @@
 // Host-side launch plans of the attention kernels: which prefill kernel a
 // shape runs (v1 / v2, workgroup width) and how many flash-decoding splits
-// a decode batch gets. Pure functions of the shape plus the tuning env
+// a decode batch gets, whether a short chunk over a long context runs the
+// append kernel and in how many splits. Pure functions of the shape plus the tuning env
 // overrides — the launchers call them, and bindings.cpp exposes them
-// (_C.prefill_plan / _C.decode_plan) so a test can assert the path a case
+// (_C.prefill_plan / _C.decode_plan / _C.append_plan) so a test can assert the path a case
 // was written for instead of trusting a comment.
 #pragma once
 
@@ -51,6 +52,17 @@ inline int env_decode_split_target() {
 }
 inline int env_decode_min_blocks_per_split() {
   static const int v = env_int("KUBEAI_DECODE_MIN_BLOCKS_PER_SPLIT", 0);
+  return v;
+}
+// split target of the append kernel (attention_append.hip): 2048 is the
+// fastest or within 3% of it at every point of the {256, 512, 1024, 2048}
+// sweep (profiles/r15_append_attention.md)
+constexpr int kAppendSplitTarget = 2048;
+inline int env_append_split_target() {
+  static const int v = []() {
+    const int t = env_int("KUBEAI_APPEND_SPLIT_TARGET", kAppendSplitTarget);
+    return t > 0 ? t : kAppendSplitTarget;
+  }();
   return v;
 }
 
@@ -128,6 +140,49 @@ inline int decode_n_splits(int B, int n_kv, int max_blocks) {
     }
   }
   return n_splits;
+}
+
+// ---- append (short chunk over a long cached context) ---------------------
+// Workgroups attention_append.hip launches before splitting: one per
+// (sequence, kv head, 16-row q tile), the tile count sized from Tq as the
+// launcher sizes its grid.
+inline int64_t append_base_wgs(int64_t Tq, int B, int n_kv) {
+  return (int64_t)B * n_kv * ((Tq + 15) / 16);
+}
+
+// decode's rule over the append grid, and at least one 32-key tile (two
+// cache blocks) per split. The target is read from the split sweep of
+// profiles/r15_append_attention.md; KUBEAI_APPEND_SPLIT_TARGET overrides it
+// for tuning sweeps.
+inline int append_n_splits(int64_t Tq, int B, int n_kv, int max_blocks) {
+  const int64_t target = env_append_split_target();
+  const int64_t base_wgs = append_base_wgs(Tq, B, n_kv);
+  int n_splits = 1;
+  if (base_wgs > 0 && base_wgs < target)
+    n_splits = (int)std::min<int64_t>(16, (target + base_wgs - 1) / base_wgs);
+  return std::min(n_splits, std::max(1, (max_blocks + 1) / 2));
+}
+
+// Smallest context (block-table width x 16, host side, no sync) from which
+// ops.paged_attention_prefill hands a shape to the append kernel under
+// KUBEAI_APPEND_ATTN=1: the smallest swept context from which the append
+// kernel is at least as fast as the route it replaces at every swept
+// (Tq, B) -- the table of profiles/r15_append_attention.md: already at 1k,
+// the smallest swept, the worst point takes 0.34x the parent route's time.
+// Shorter contexts were not swept and stay where they are.
+constexpr int kAppendMinCtx = 1024;
+
+// Whether the append kernel takes the shape: inside its scope, underfilling
+// the 256-CU chip before splitting, over a context long enough to split.
+inline bool append_takes(int64_t Tq, int B, int n_q, int n_kv, int hd,
+                         int max_blocks, int64_t window, double softcap) {
+  if (n_kv <= 0 || n_q % n_kv != 0) return false;
+  const int G = n_q / n_kv;
+  if (hd != 128 || window != 0 || softcap != 0.0) return false;
+  if (G != 1 && G != 2 && G != 4 && G != 8) return false;
+  if (Tq < 1 || B < 1) return false;
+  if (append_base_wgs(Tq, B, n_kv) >= 256) return false;
+  return (int64_t)max_blocks * kBlockSize >= kAppendMinCtx;
 }
 
 }  // namespace attn_plan

@@ -41,6 +41,14 @@ void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
                              torch::Tensor query_start_loc,
                              torch::Tensor seq_lens, double scale,
                              int64_t window, double softcap);
+// split-KV attention of a short chunk over a long cached context
+// (attention_append.hip)
+void paged_attention_append(torch::Tensor out, torch::Tensor q,
+                            torch::Tensor k_cache, torch::Tensor v_cache,
+                            torch::Tensor block_tables,
+                            torch::Tensor query_start_loc,
+                            torch::Tensor seq_lens, double scale,
+                            int64_t n_splits, int64_t window, double softcap);
 void silu_and_mul(torch::Tensor out, torch::Tensor x);
 void gelu_and_mul(torch::Tensor out, torch::Tensor x);
 void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w);
@@ -150,6 +158,15 @@ static std::pair<int64_t, int64_t> prefill_plan(int64_t Tq, int64_t B,
 static int64_t decode_plan(int64_t B, int64_t n_kv, int64_t max_blocks) {
   return attn_plan::decode_n_splits((int)B, (int)n_kv, (int)max_blocks);
 }
+static std::pair<bool, int64_t> append_plan(int64_t Tq, int64_t B, int64_t n_q,
+                                            int64_t n_kv, int64_t hd,
+                                            int64_t max_blocks, int64_t window,
+                                            double softcap) {
+  TORCH_CHECK(n_kv > 0 && n_q % n_kv == 0);
+  return {attn_plan::append_takes(Tq, (int)B, (int)n_q, (int)n_kv, (int)hd,
+                                  (int)max_blocks, window, softcap),
+          attn_plan::append_n_splits(Tq, (int)B, (int)n_kv, (int)max_blocks)};
+}
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("prefill_plan", &prefill_plan,
@@ -162,6 +179,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flash-decoding splits paged_attention_decode launches",
         pybind11::arg("B"), pybind11::arg("n_kv"),
         pybind11::arg("max_blocks"));
+  m.def("append_plan", &append_plan,
+        "(taken under KUBEAI_APPEND_ATTN=1, KV splits) of "
+        "paged_attention_append",
+        pybind11::arg("Tq"), pybind11::arg("B"), pybind11::arg("n_q"),
+        pybind11::arg("n_kv"), pybind11::arg("hd"),
+        pybind11::arg("max_blocks"), pybind11::arg("window") = 0,
+        pybind11::arg("softcap") = 0.0);
   m.def("rmsnorm", &rmsnorm, "RMSNorm (bf16, fp32 accum)");
   m.def("fused_add_rmsnorm", &fused_add_rmsnorm,
         "in-place residual add + RMSNorm");
@@ -179,6 +203,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "decode attention kernel (q, k, v are only read)");
   m.def("paged_attention_prefill", &paged_attention_prefill,
         "paged causal flash attention over cached KV");
+  m.def("paged_attention_append", &paged_attention_append,
+        "split-KV paged causal attention of a short chunk over a long cached "
+        "context (hd 128, no window / softcap); n_splits = 0 takes "
+        "append_plan's",
+        pybind11::arg("out"), pybind11::arg("q"), pybind11::arg("k_cache"),
+        pybind11::arg("v_cache"), pybind11::arg("block_tables"),
+        pybind11::arg("query_start_loc"), pybind11::arg("seq_lens"),
+        pybind11::arg("scale"), pybind11::arg("n_splits") = 0,
+        pybind11::arg("window") = 0, pybind11::arg("softcap") = 0.0);
   m.def("gelu_and_mul", &gelu_and_mul, "GeGLU tanh-gelu(gate)*up");
   m.def("silu_and_mul", &silu_and_mul, "SwiGLU activation");
   m.def("skinny_gemm", &skinny_gemm, "weight-streaming GEMM for M<=64");

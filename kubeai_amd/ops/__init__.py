@@ -197,12 +197,57 @@ def rope_cache_attention_decode(
     )
 
 
+def append_attn() -> bool:
+    """KUBEAI_APPEND_ATTN=1 lets paged_attention_prefill hand the shapes
+    _C.append_plan takes (a short chunk over a long cached context) to
+    paged_attention_append. Off by default: it moves low bits of prefill
+    outputs. Read at call time: the routing test and A/B runs flip it."""
+    return os.environ.get("KUBEAI_APPEND_ATTN", "0") == "1"
+
+
+def paged_attention_append(
+    q, k_cache, v_cache, block_tables, query_start_loc, seq_lens, scale: float,
+    out=None, n_splits: int = 0, window: int = 0, softcap: float = 0.0,
+):
+    """paged_attention_prefill's semantics on the split-KV kernel for a few
+    new query rows per sequence over a long cache (attention_append.hip):
+    head_dim 128, G in {1, 2, 4, 8}, bf16 or e5m2 cache; a window, a softcap
+    or any other shape is a RuntimeError. q may be a row-strided view of the
+    fused qkv output. n_splits = 0 takes _C.append_plan's split count
+    (1..16 forces one)."""
+    if q.is_cuda:
+        _require_ext()
+        if out is None:
+            out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        _C.paged_attention_append(
+            out, q, k_cache, v_cache, block_tables, query_start_loc, seq_lens,
+            scale, n_splits, window, softcap
+        )
+        return out
+    res = ref.paged_attention_prefill(
+        q, k_cache, v_cache, block_tables, query_start_loc, seq_lens, scale,
+        window=window, softcap=softcap,
+    )
+    if out is not None:
+        out.copy_(res)
+        return out
+    return res
+
+
 def paged_attention_prefill(
     q, k_cache, v_cache, block_tables, query_start_loc, seq_lens, scale: float,
     out=None, window: int = 0, softcap: float = 0.0,
 ):
     if q.is_cuda:
         _require_ext()
+        if append_attn() and _C.append_plan(
+            q.shape[0], seq_lens.shape[0], q.shape[1], k_cache.shape[1],
+            q.shape[2], block_tables.shape[1], window, softcap
+        )[0]:
+            return paged_attention_append(
+                q, k_cache, v_cache, block_tables, query_start_loc, seq_lens,
+                scale, out=out,
+            )
         if out is None:
             out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
         _C.paged_attention_prefill(
