@@ -13,7 +13,11 @@
 // The fp8 variants quantize inside the PRODUCING op, so the W8A8 path pays
 // no extra launch or HBM round trip for its dynamic activation scales.
 // Scale convention: common.h::row_scale_fp8 (matches torch's
-// .to(float8_e4m3fn) + torch._scaled_mm rowwise scale_a).
+// .to(float8_e4m3fn) + torch._scaled_mm rowwise scale_a). That is the
+// multiplication form, x * (448 / amax); ref.quant_fp8 is written in the
+// division form, x / (amax / 448): equal scales, and bytes that can differ
+// by one code near a rounding tie. Only quant_fp8_div and
+// fused_add_rmsnorm_fp8_div evaluate the division form.
 //
 // The row stays in registers between the block reductions: the per-thread
 // iteration count is a template parameter and every loop over it is fully
@@ -275,25 +279,47 @@ void dispatch_row(const int nvec, Launch&& launch) {
 
 // x is [T, in_width * W] bf16, W the output row length
 void check_row_op(const torch::Tensor& x, const int64_t W) {
-  TORCH_CHECK(x.is_contiguous());
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous());
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(W % 8 == 0 && W <= kMaxH);
+  TORCH_CHECK(W > 0 && W % 8 == 0 && W <= kMaxH);
 }
 
-// x is the [T, H] input, or (ids set) the [V, H] table its rows come from
+// t is a contiguous bf16 tensor of n elements on x's device
+void check_bf16(const torch::Tensor& t, const torch::Tensor& x,
+                const int64_t n) {
+  TORCH_CHECK(t.device() == x.device() && t.is_contiguous());
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16 && t.numel() == n);
+}
+
+// what an fp8 producer fills for T rows of W: out, T * W one-byte elements,
+// and out_scale, T floats
+void check_fp8_rows(const torch::Tensor& out, const torch::Tensor& out_scale,
+                    const torch::Tensor& x, const int64_t T, const int64_t W) {
+  TORCH_CHECK(out.device() == x.device() && out.is_contiguous());
+  TORCH_CHECK(out.element_size() == 1 && out.numel() == T * W);
+  TORCH_CHECK(out_scale.device() == x.device() && out_scale.is_contiguous());
+  TORCH_CHECK(out_scale.scalar_type() == torch::kFloat32 &&
+              out_scale.numel() == T);
+}
+
+// x is the [T, H] input, or (ids set) the [V, H] table its rows come from.
+// Every argument is validated before the launch, and T = 0 launches nothing.
 template <bool kFused, bool kFp8Out, bool kDiv = false, bool kEmbed = false>
-void launch_rmsnorm(void* out, float* out_scale, const torch::Tensor& x,
-                    void* residual, const torch::Tensor& weight, double eps,
+void launch_rmsnorm(const torch::Tensor& out, const torch::Tensor* out_scale,
+                    const torch::Tensor& x, const torch::Tensor* residual,
+                    const torch::Tensor& weight, double eps,
                     const torch::Tensor* ids = nullptr,
                     const bool write_rows = true) {
-  const int H = x.size(-1);
-  check_row_op(x, H);
-  const int T = kEmbed ? ids->numel() : x.numel() / H;
-  if constexpr (kDiv || kEmbed) {
-    TORCH_CHECK(weight.is_contiguous() && weight.numel() == H &&
-                weight.scalar_type() == torch::kBFloat16);
-    if (T == 0) return;
-  }
+  TORCH_CHECK(x.dim() >= 1);
+  const int64_t width = x.size(-1);
+  check_row_op(x, width);
+  const int H = (int)width;
+  const int64_t T = kEmbed ? ids->numel() : x.numel() / H;
+  check_bf16(weight, x, H);
+  if constexpr (kFp8Out) check_fp8_rows(out, *out_scale, x, T, H);
+  else check_bf16(out, x, T * H);
+  if constexpr (kFused || kEmbed) check_bf16(*residual, x, T * H);
+  if (T == 0) return;
   using out_t = std::conditional_t<kFp8Out, unsigned char, ushort>;
   dispatch_row<RowPolicy::kNorm>(H / 8, [&](auto threads, auto iters) {
     constexpr int kThreads = decltype(threads)::value;
@@ -301,7 +327,10 @@ void launch_rmsnorm(void* out, float* out_scale, const torch::Tensor& x,
     hipLaunchKernelGGL(
         (rmsnorm_kernel<kFused, kFp8Out, kThreads, kIters, kDiv, kEmbed>),
         dim3(T), dim3(kThreads), 0, c10::hip::getCurrentHIPStream().stream(),
-        (out_t*)out, out_scale, (ushort*)x.data_ptr(), (ushort*)residual,
+        (out_t*)out.data_ptr(),
+        kFp8Out ? out_scale->data_ptr<float>() : nullptr,
+        (ushort*)x.data_ptr(),
+        (kFused || kEmbed) ? (ushort*)residual->data_ptr() : nullptr,
         (const ushort*)weight.data_ptr(), (float)eps, H,
         kEmbed ? ids->data_ptr<int32_t>() : nullptr,
         kEmbed ? (int)x.size(0) : 0, write_rows);
@@ -312,10 +341,13 @@ void launch_rmsnorm(void* out, float* out_scale, const torch::Tensor& x,
 template <typename Producer, bool kDiv = false>
 void launch_row_fp8(torch::Tensor& out, torch::Tensor& out_scale,
                     const torch::Tensor& x) {
-  const int W = x.size(-1) / Producer::kInWidth;
-  check_row_op(x, W);
-  TORCH_CHECK(x.size(-1) == (int64_t)W * Producer::kInWidth);
-  const int T = x.numel() / x.size(-1);
+  TORCH_CHECK(x.dim() >= 1);
+  const int64_t width = x.size(-1) / Producer::kInWidth;
+  check_row_op(x, width);
+  TORCH_CHECK(x.size(-1) == width * Producer::kInWidth);
+  const int W = (int)width;
+  const int64_t T = x.numel() / x.size(-1);
+  check_fp8_rows(out, out_scale, x, T, W);
   if (T == 0) return;
   dispatch_row<RowPolicy::kMax>(W / 8, [&](auto threads, auto iters) {
     constexpr int kThreads = decltype(threads)::value;
@@ -334,29 +366,23 @@ void launch_row_fp8(torch::Tensor& out, torch::Tensor& out_scale,
 
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor weight,
              double eps) {
-  TORCH_CHECK(out.is_contiguous());
-  launch_rmsnorm<false, false>(out.data_ptr(), nullptr, x, nullptr, weight, eps);
+  launch_rmsnorm<false, false>(out, nullptr, x, nullptr, weight, eps);
 }
 
 void fused_add_rmsnorm(torch::Tensor x, torch::Tensor residual,
                        torch::Tensor weight, double eps) {
-  TORCH_CHECK(residual.is_contiguous());
-  launch_rmsnorm<true, false>(x.data_ptr(), nullptr, x, residual.data_ptr(),
-                              weight, eps);
+  launch_rmsnorm<true, false>(x, nullptr, x, &residual, weight, eps);
 }
 
 void rmsnorm_fp8(torch::Tensor out, torch::Tensor out_scale, torch::Tensor x,
                  torch::Tensor weight, double eps) {
-  launch_rmsnorm<false, true>(out.data_ptr(), out_scale.data_ptr<float>(), x,
-                              nullptr, weight, eps);
+  launch_rmsnorm<false, true>(out, &out_scale, x, nullptr, weight, eps);
 }
 
 void fused_add_rmsnorm_fp8(torch::Tensor out, torch::Tensor out_scale,
                            torch::Tensor x, torch::Tensor residual,
                            torch::Tensor weight, double eps) {
-  TORCH_CHECK(residual.is_contiguous());
-  launch_rmsnorm<true, true>(out.data_ptr(), out_scale.data_ptr<float>(), x,
-                             residual.data_ptr(), weight, eps);
+  launch_rmsnorm<true, true>(out, &out_scale, x, &residual, weight, eps);
 }
 
 // (out, out_scale) = quant_fp8_div of the row fused_add_rmsnorm would leave
@@ -366,16 +392,9 @@ void fused_add_rmsnorm_fp8_div(torch::Tensor out, torch::Tensor out_scale,
                                torch::Tensor x, torch::Tensor residual,
                                torch::Tensor weight, double eps,
                                bool write_rows) {
-  TORCH_CHECK(residual.is_contiguous() && residual.sizes() == x.sizes() &&
-              residual.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(out.is_contiguous() && out.numel() == x.numel() &&
-              out.element_size() == 1);
-  TORCH_CHECK(out_scale.is_contiguous() &&
-              out_scale.scalar_type() == torch::kFloat32 &&
-              out_scale.numel() * x.size(-1) == x.numel());
-  launch_rmsnorm<true, true, true>(out.data_ptr(), out_scale.data_ptr<float>(),
-                                   x, residual.data_ptr(), weight, eps, nullptr,
-                                   write_rows);
+  TORCH_CHECK(residual.sizes() == x.sizes());
+  launch_rmsnorm<true, true, true>(out, &out_scale, x, &residual, weight, eps,
+                                   nullptr, write_rows);
 }
 
 // x_out[t] = table[ids[t]] (ids clamped into the table), and (out, out_scale)
@@ -385,18 +404,12 @@ void embed_rmsnorm_fp8(torch::Tensor out, torch::Tensor out_scale,
                        torch::Tensor table, torch::Tensor weight, double eps) {
   TORCH_CHECK(table.dim() == 2 && table.size(0) >= 1);
   TORCH_CHECK(ids.dim() == 1 && ids.is_contiguous() &&
-              ids.scalar_type() == torch::kInt32);
-  const int64_t T = ids.numel(), H = table.size(1);
-  TORCH_CHECK(x_out.is_contiguous() && x_out.dim() == 2 && x_out.size(0) == T &&
-              x_out.size(1) == H && x_out.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(out.is_contiguous() && out.numel() == T * H &&
-              out.element_size() == 1);
-  TORCH_CHECK(out_scale.is_contiguous() &&
-              out_scale.scalar_type() == torch::kFloat32 &&
-              out_scale.numel() == T);
-  launch_rmsnorm<false, true, false, true>(
-      out.data_ptr(), out_scale.data_ptr<float>(), table, x_out.data_ptr(),
-      weight, eps, &ids);
+              ids.scalar_type() == torch::kInt32 &&
+              ids.device() == table.device());
+  TORCH_CHECK(x_out.dim() == 2 && x_out.size(0) == ids.numel() &&
+              x_out.size(1) == table.size(1));
+  launch_rmsnorm<false, true, false, true>(out, &out_scale, table, &x_out,
+                                           weight, eps, &ids);
 }
 
 void silu_and_mul_fp8(torch::Tensor out, torch::Tensor out_scale,

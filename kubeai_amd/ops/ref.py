@@ -518,8 +518,14 @@ def topk_topp_sample(
 
 
 def quant_fp8(x: torch.Tensor):
-    """Per-row dynamic OCP-e4m3 quantization (CPU reference of
-    csrc/row_kernels.hip::quant_fp8): scale = amax/448, symmetric."""
+    """Per-row dynamic OCP-e4m3 quantization, scale = amax/448, symmetric.
+
+    This is the DIVISION form, q = e4m3(x / scale). The kernel of the same
+    name (csrc/row_kernels.hip::quant_fp8, common.h::row_scale_fp8) is the
+    MULTIPLICATION form, q = e4m3(x * (448 / amax)): the scales are equal,
+    but x / scale and x * (448 / amax) round differently in fp32, so near a
+    rounding tie a byte can differ by one code. The kernel's own arithmetic
+    is tests/row_oracle.py::exact_bytes(x, "mul")."""
     xf = x.float()
     amax = xf.abs().amax(dim=-1).clamp_min(1e-6)
     scale = amax / 448.0

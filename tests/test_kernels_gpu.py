@@ -294,11 +294,21 @@ def test_quant_fp8_roundtrip():
     x = torch.randn(21, 4096, dtype=torch.bfloat16, device=DEV) * 3
     q8, scale = ops.quant_fp8(x)
     torch.testing.assert_close(_dequant(q8, scale), x.float(), atol=0.1, rtol=0.07)
-    # matches torch's cast given the same scale
+    # matches torch's cast given the same scale: this reference is the
+    # division form, the kernel the multiplication form, hence the allowance
     expected_q = (x.float() / scale.view(-1, 1)).clamp(-448, 448).to(
         torch.float8_e4m3fn
     )
     assert (q8.view(torch.uint8) == expected_q.view(torch.uint8)).float().mean() > 0.99
+    # in the kernel's own form every byte and every scale bit is pinned
+    # (test_row_kernels_gpu.py does this at every dispatch width)
+    xc = x.float().cpu()
+    amax = xc.abs().amax(-1, keepdim=True).clamp_min(1e-6)
+    exact_q = (xc * (torch.tensor(448.0) / amax)).clamp(-448, 448).to(
+        torch.float8_e4m3fn
+    )
+    assert torch.equal(q8.cpu().view(torch.uint8), exact_q.view(torch.uint8))
+    assert torch.equal(scale.cpu(), (amax / torch.tensor(448.0)).view(-1))
 
 
 def test_greedy_sample():
