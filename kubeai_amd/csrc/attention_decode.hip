@@ -709,8 +709,8 @@ struct RawQKV {
 // K/V rows into the caches inside the decode kernel.
 //
 // Instantiation set of paged_decode_kernel: the value lists of the nested
-// dispatch below, G {1,2,4,5,6,8} x hd {128,256} x cache type x CAP x RAW
-// (96); of the merge kernels: hd x split tier {8,16} (4), and x passes {1,2}
+// dispatch below, G {1,2,4,5,6,7,8} x hd {128,256} x cache type x CAP x RAW
+// (112); of the merge kernels: hd x split tier {8,16} (4), and x passes {1,2}
 // for the fp8 form (8).
 void decode_impl(torch::Tensor out, const c10::optional<torch::Tensor>& out_fp8,
                  const c10::optional<torch::Tensor>& out_scale, torch::Tensor q,
@@ -787,7 +787,7 @@ void decode_impl(torch::Tensor out, const c10::optional<torch::Tensor>& out_fp8,
   dim3 grid(B * n_kv * n_splits), block(kBlockThreads);
   auto stream = c10::hip::getCurrentHIPStream().stream();
   // hd 256 is the gemma2 shape (G <= 2 in practice)
-  dispatch_int<1, 2, 4, 5, 6, 8>(s.G, "GQA group size", [&](auto g) {
+  dispatch_int<1, 2, 4, 5, 6, 7, 8>(s.G, "GQA group size", [&](auto g) {
     dispatch_int<128, 256>(hd, "head dim", [&](auto hdv) {
       dispatch_bool(s.fp8_cache, [&](auto fp8) {
         dispatch_bool(softcap > 0.0, [&](auto cap) {

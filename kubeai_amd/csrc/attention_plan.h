@@ -1,10 +1,12 @@
 // Host-side launch plans of the attention kernels: which prefill kernel a
 // shape runs (v1 / v2, workgroup width) and how many flash-decoding splits
 // a decode batch gets, whether a short chunk over a long context runs the
-// append kernel and in how many splits. Pure functions of the shape plus the tuning env
+// append kernel and in how many splits, whether the packed-row kernel takes a
+// group size and at which width. Pure functions of the shape plus the tuning env
 // overrides — the launchers call them, and bindings.cpp exposes them
-// (_C.prefill_plan / _C.decode_plan / _C.append_plan) so a test can assert the path a case
-// was written for instead of trusting a comment.
+// (_C.prefill_plan / _C.decode_plan / _C.append_plan / _C.packed_prefill_plan)
+// so a test can assert the path a case was written for instead of trusting a
+// comment.
 #pragma once
 
 #include <algorithm>
@@ -115,6 +117,28 @@ inline PrefillPlan prefill_plan(int64_t Tq, int B, int n_q, int n_kv, int hd,
     if (nw) return {2, nw};
   }
   return {1, n_q / n_kv};
+}
+
+// ---- packed-row prefill (attention_prefill_packed.hip) -------------------
+// The group sizes that divide no v2 wave map, at hd 128 without window or
+// softcap. paged_attention_prefill asks this first; everything it takes
+// raised "unsupported GQA group size" before the kernel existed, so no shape
+// v1 or v2 serve is rerouted.
+inline bool packed_takes(int n_q, int n_kv, int hd, int64_t window,
+                         double softcap) {
+  if (n_kv <= 0 || n_q % n_kv != 0) return false;
+  const int G = n_q / n_kv;
+  return hd == 128 && window == 0 && softcap == 0.0 && G >= 5 && G <= 7;
+}
+
+// Workgroup width: 8 waves (256 virtual rows) for every shape. v2's underfill
+// rule (4 waves when B * n_kv * ceil(Tq * G / 256) < 256) was measured for
+// this kernel with a 4-wave instantiation: 8 waves were as fast or faster at
+// every point, from 40 workgroups (Tq = 512, n_kv = 4) up
+// (profiles/r16_packed_gqa.md), so the 4-wave form is not built. The shape
+// arguments stay: a rule that reads them again changes this function only.
+inline int packed_waves(int64_t /*Tq*/, int /*B*/, int /*n_q*/, int /*n_kv*/) {
+  return 8;
 }
 
 // ---- decode ---------------------------------------------------------------

@@ -306,6 +306,15 @@ void paged_attention_prefill_v2(torch::Tensor out, torch::Tensor q,
                                 torch::Tensor seq_lens, double scale,
                                 const AttnShape& s, int nw);
 
+// attention_prefill_packed.hip: G = 5, 6, 7; s = the validated shape
+void paged_attention_prefill_packed(torch::Tensor out, torch::Tensor q,
+                                    torch::Tensor k_cache,
+                                    torch::Tensor v_cache,
+                                    torch::Tensor block_tables,
+                                    torch::Tensor query_start_loc,
+                                    torch::Tensor seq_lens, double scale,
+                                    const AttnShape& s);
+
 void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
                              torch::Tensor k_cache, torch::Tensor v_cache,
                              torch::Tensor block_tables,
@@ -318,6 +327,14 @@ void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
   const int n_kv = s.n_kv, max_blocks = s.max_blocks;
   const int B = seq_lens.size(0);
   if (q.size(0) == 0) return;
+  // G = 5, 6, 7 at hd 128 without window or softcap: the packed-row kernel.
+  // Asked first; it takes only shapes that have no v1 / v2 instantiation
+  // (with a window or a softcap they still end in the dispatch error below).
+  if (attn_plan::packed_takes(s.n_q, n_kv, s.hd, window, softcap)) {
+    paged_attention_prefill_packed(out, q, k_cache, v_cache, block_tables,
+                                   query_start_loc, seq_lens, scale, s);
+    return;
+  }
   // v2: 8-wave 32x32-MFMA ladder (attention_prefill_v2.hip), G in
   // {1,2,4,8} — DEFAULT (1.5-1.8x v1 after the defer-max/VALU pass:
   // 268 TF vs 150 @Tq=8192, numerics cos=1.0 across the full isolation

@@ -3,8 +3,8 @@
 // GQA D=128 shape in plain HIP), re-derived for the PAGED KV setting.
 //
 // Semantics: kubeai_amd/ops/ref.py::paged_attention_prefill (identical
-// to attention_prefill.hip v1; v1 remains the fallback for odd GQA
-// group sizes).
+// to attention_prefill.hip v1). G in {1, 2, 4, 8} only, like v1; G = 5, 6
+// and 7 run attention_prefill_packed.hip, any other G is a host error.
 //
 // Structure (per workgroup = (seq, kv_head, q-chunk), 8 waves):
 //  - waves = G heads x (8/G) 32-row q subtiles; all 8 share each staged

@@ -209,6 +209,23 @@ PRESETS: dict[str, ModelArchConfig] = {
         tie_word_embeddings=True,
         rope_theta=1000000.0,
     ),
+    # qwen2-tiny at the 7B models' GQA group size (7 query heads per KV
+    # head): the packed-row prefill kernel and the G = 7 decode at test size
+    "qwen2-tiny-g7": ModelArchConfig(
+        vocab_size=2048,
+        hidden_size=256,
+        intermediate_size=512,
+        num_hidden_layers=2,
+        num_attention_heads=7,
+        num_key_value_heads=1,
+        head_dim=128,
+        max_position_embeddings=2048,
+        bos_token_id=1,
+        eos_token_id=2,
+        attention_bias=True,
+        tie_word_embeddings=True,
+        rope_theta=1000000.0,
+    ),
     "qwen2-7b": ModelArchConfig(
         vocab_size=152064,
         hidden_size=3584,
