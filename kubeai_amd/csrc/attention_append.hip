@@ -417,7 +417,9 @@ void paged_attention_append(torch::Tensor out, torch::Tensor q,
                             int64_t n_splits, int64_t window, double softcap) {
   const AttnShape s =
       check_paged_attention(out, q, k_cache, v_cache, block_tables, seq_lens);
-  TORCH_CHECK(s.hd == kHD, "paged_attention_append supports head_dim 128");
+  TORCH_CHECK(s.hd == kHD,
+              "paged_attention_append supports head_dim 128, not head_dim ",
+              s.hd);
   TORCH_CHECK(window == 0 && softcap == 0.0,
               "paged_attention_append supports neither window nor softcap");
   TORCH_CHECK(s.G == 1 || s.G == 2 || s.G == 4 || s.G == 8,

@@ -32,12 +32,25 @@ inline AttnShape check_paged_attention(const torch::Tensor& out,
   const int n_q = q.size(1), hd = q.size(2);
   const int n_kv = k_cache.size(1);
   const int max_blocks = block_tables.size(1);
-  TORCH_CHECK(hd == 128 || hd == 256,
-              "paged attention supports head_dim 128 or 256");
+  TORCH_CHECK(hd == 64 || hd == 128 || hd == 256,
+              "paged attention supports head_dim 64, 128 or 256");
   TORCH_CHECK(k_cache.size(2) == attn_plan::kBlockSize,
               "paged attention supports block_size=16");
   TORCH_CHECK(n_q % n_kv == 0);
   return {n_q, n_kv, hd, n_q / n_kv, max_blocks, fp8_cache};
+}
+
+// head_dim 64 runs on the hd-64 kernels only (attention_decode_hd64.hip,
+// attention_prefill_hd64.hip): causal, no window, no softcap, G in
+// {1, 2, 4, 7, 8}. Anything else at hd 64 is an error here, before a launch.
+inline void check_hd64_scope(const AttnShape& s, int64_t window,
+                             double softcap, const char* op) {
+  if (s.hd != 64) return;
+  TORCH_CHECK(window == 0 && softcap == 0.0, op,
+              ": head_dim 64 supports neither window nor softcap");
+  TORCH_CHECK(attn_plan::hd64_group(s.G), op,
+              ": head_dim 64 supports GQA group sizes 1, 2, 4, 7 and 8, not ",
+              s.G);
 }
 
 // (out_fp8, out_scale): the e4m3 row quantization of `out` viewed as

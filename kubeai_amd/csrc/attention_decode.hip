@@ -613,11 +613,15 @@ __global__ void decode_merge_kernel(
     const float* __restrict__ part_o,     // [B, n_q, n_splits, hd]
     const float* __restrict__ part_ml,    // [B, n_q, n_splits, 2]
     const int n_q, const int n_splits, const int64_t n_bh) {
-  constexpr int EPL = HD / 64;
+  // elements per lane; at hd 64 the first 32 lanes own a pair each
+  constexpr int EPL = HD >= 128 ? HD / 64 : 2;
   const int64_t bh = (int64_t)blockIdx.x * (blockDim.x / WAVE_SIZE) +
                      threadIdx.x / WAVE_SIZE;
   if (bh >= n_bh) return;
   const int lane = threadIdx.x % WAVE_SIZE;
+  if constexpr (HD < 128) {
+    if (lane >= HD / EPL) return;
+  }
   uint32_t packed[EPL / 2];
   merge_partials<EPL, HD, SCAP>(part_o + bh * n_splits * HD + EPL * lane,
                                 part_ml + bh * n_splits * 2, n_splits, packed);
@@ -696,6 +700,15 @@ __launch_bounds__(kMergeMaxThreads) __global__ void decode_merge_fp8_kernel(
 
 void quant_fp8(torch::Tensor out, torch::Tensor out_scale, torch::Tensor x);
 
+// attention_decode_hd64.hip: the hd-64 decode kernel; s = the validated
+// shape, part_o / part_ml null when n_splits == 1
+void paged_attention_decode_hd64(torch::Tensor out, torch::Tensor q,
+                                 torch::Tensor k_cache, torch::Tensor v_cache,
+                                 torch::Tensor block_tables,
+                                 torch::Tensor seq_lens, double scale,
+                                 const AttnShape& s, int n_splits,
+                                 float* part_o, float* part_ml);
+
 namespace {
 
 // The extra inputs of the raw-qkv mode (rope_cache_attention_decode)
@@ -710,8 +723,10 @@ struct RawQKV {
 //
 // Instantiation set of paged_decode_kernel: the value lists of the nested
 // dispatch below, G {1,2,4,5,6,7,8} x hd {128,256} x cache type x CAP x RAW
-// (112); of the merge kernels: hd x split tier {8,16} (4), and x passes {1,2}
-// for the fp8 form (8).
+// (112); of the merge kernels: hd {64,128,256} x split tier {8,16} (6), and
+// x passes {1,2} for the fp8 form (12). hd 64 runs paged_decode_hd64_kernel
+// (attention_decode_hd64.hip) and shares the split plan, the partial buffers
+// and the merge kernels; it has no window, softcap or raw-qkv form.
 void decode_impl(torch::Tensor out, const c10::optional<torch::Tensor>& out_fp8,
                  const c10::optional<torch::Tensor>& out_scale, torch::Tensor q,
                  torch::Tensor k_cache, torch::Tensor v_cache,
@@ -723,6 +738,10 @@ void decode_impl(torch::Tensor out, const c10::optional<torch::Tensor>& out_fp8,
   const int B = q.size(0), n_q = s.n_q, n_kv = s.n_kv, hd = s.hd;
   const int max_blocks = s.max_blocks;
   TORCH_CHECK(seq_lens.numel() >= B && block_tables.size(0) >= B);
+  check_hd64_scope(s, window, softcap, "paged_attention_decode");
+  TORCH_CHECK(hd != 64 || raw == nullptr,
+              "rope_cache_attention_decode: head_dim 64 has no fused rope "
+              "form, run rope_and_cache and paged_attention_decode");
   const bool want_fp8 = out_fp8.has_value();
   if (want_fp8) {
     TORCH_CHECK(out_scale.has_value());
@@ -786,6 +805,11 @@ void decode_impl(torch::Tensor out, const c10::optional<torch::Tensor>& out_fp8,
   }
   dim3 grid(B * n_kv * n_splits), block(kBlockThreads);
   auto stream = c10::hip::getCurrentHIPStream().stream();
+  if (hd == 64) {
+    paged_attention_decode_hd64(out, q, k_cache, v_cache, block_tables,
+                                seq_lens, scale, s, n_splits, part_o_ptr,
+                                part_ml_ptr);
+  } else
   // hd 256 is the gemma2 shape (G <= 2 in practice)
   dispatch_int<1, 2, 4, 5, 6, 7, 8>(s.G, "GQA group size", [&](auto g) {
     dispatch_int<128, 256>(hd, "head dim", [&](auto hdv) {
@@ -820,7 +844,7 @@ void decode_impl(torch::Tensor out, const c10::optional<torch::Tensor>& out_fp8,
   TORCH_CHECK(n_splits <= kMergeSplitCapHi);
   // fp8 in the merge: needs a row within the fused kernel's bound
   const bool fuse_fp8 = want_fp8 && (int64_t)n_q * hd <= kMergeRowMax;
-  dispatch_int<128, 256>(hd, "head dim", [&](auto hdv) {
+  dispatch_int<64, 128, 256>(hd, "head dim", [&](auto hdv) {
     // split-bound tier of the merge kernels
     dispatch_bool(n_splits <= kMergeSplitCapLo, [&](auto lo) {
       constexpr int HD = decltype(hdv)::value;

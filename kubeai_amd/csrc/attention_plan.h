@@ -4,8 +4,8 @@
 // append kernel and in how many splits, whether the packed-row kernel takes a
 // group size and at which width. Pure functions of the shape plus the tuning env
 // overrides — the launchers call them, and bindings.cpp exposes them
-// (_C.prefill_plan / _C.decode_plan / _C.append_plan / _C.packed_prefill_plan)
-// so a test can assert the path a case was written for instead of trusting a
+// (_C.prefill_plan / _C.decode_plan / _C.append_plan / _C.packed_prefill_plan
+// / _C.hd64_prefill_plan) so a test can assert the path a case was written for instead of trusting a
 // comment.
 #pragma once
 
@@ -138,6 +138,28 @@ inline bool packed_takes(int n_q, int n_kv, int hd, int64_t window,
 // (profiles/r16_packed_gqa.md), so the 4-wave form is not built. The shape
 // arguments stay: a rule that reads them again changes this function only.
 inline int packed_waves(int64_t /*Tq*/, int /*B*/, int /*n_q*/, int /*n_kv*/) {
+  return 8;
+}
+
+// ---- head_dim 64 (attention_prefill_hd64.hip, attention_decode_hd64.hip) --
+// The group sizes the hd-64 kernels are built for: MHA, Llama-3.2-1B (4),
+// Qwen2 / Qwen2.5-0.5B (7), TinyLlama (8), and 2.
+inline bool hd64_group(int G) {
+  return G == 1 || G == 2 || G == 4 || G == 7 || G == 8;
+}
+
+// Whether the hd-64 prefill kernel takes the shape. paged_attention_prefill
+// asks this before any other route; every hd-64 shape raised before the
+// kernel existed, so nothing v1, v2 or the packed kernel serve is rerouted.
+inline bool hd64_takes(int n_q, int n_kv, int hd, int64_t window,
+                       double softcap) {
+  if (n_kv <= 0 || n_q % n_kv != 0) return false;
+  return hd == 64 && window == 0 && softcap == 0.0 && hd64_group(n_q / n_kv);
+}
+
+// Workgroup width of the hd-64 prefill kernel: 8 waves (256 virtual rows) for
+// every shape, as the packed-row kernel it shares its row map with.
+inline int hd64_waves(int64_t /*Tq*/, int /*B*/, int /*n_q*/, int /*n_kv*/) {
   return 8;
 }
 

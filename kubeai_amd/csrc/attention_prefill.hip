@@ -315,6 +315,14 @@ void paged_attention_prefill_packed(torch::Tensor out, torch::Tensor q,
                                     torch::Tensor seq_lens, double scale,
                                     const AttnShape& s);
 
+// attention_prefill_hd64.hip: hd 64, G in {1,2,4,7,8}; s = the validated shape
+void paged_attention_prefill_hd64(torch::Tensor out, torch::Tensor q,
+                                  torch::Tensor k_cache, torch::Tensor v_cache,
+                                  torch::Tensor block_tables,
+                                  torch::Tensor query_start_loc,
+                                  torch::Tensor seq_lens, double scale,
+                                  const AttnShape& s);
+
 void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
                              torch::Tensor k_cache, torch::Tensor v_cache,
                              torch::Tensor block_tables,
@@ -326,7 +334,16 @@ void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
   TORCH_CHECK(query_start_loc.scalar_type() == torch::kInt32);
   const int n_kv = s.n_kv, max_blocks = s.max_blocks;
   const int B = seq_lens.size(0);
+  // hd 64 has one kernel and nothing else: out of its scope is an error
+  check_hd64_scope(s, window, softcap, "paged_attention_prefill");
   if (q.size(0) == 0) return;
+  // hd 64: asked before any other route; every shape it takes raised before
+  // the kernel existed
+  if (attn_plan::hd64_takes(s.n_q, n_kv, s.hd, window, softcap)) {
+    paged_attention_prefill_hd64(out, q, k_cache, v_cache, block_tables,
+                                 query_start_loc, seq_lens, scale, s);
+    return;
+  }
   // G = 5, 6, 7 at hd 128 without window or softcap: the packed-row kernel.
   // Asked first; it takes only shapes that have no v1 / v2 instantiation
   // (with a window or a softcap they still end in the dispatch error below).

@@ -176,6 +176,14 @@ static std::pair<bool, int64_t> packed_prefill_plan(
                                   softcap),
           attn_plan::packed_waves(Tq, (int)B, (int)n_q, (int)n_kv)};
 }
+static std::pair<bool, int64_t> hd64_prefill_plan(
+    int64_t Tq, int64_t B, int64_t n_q, int64_t n_kv, int64_t hd,
+    int64_t max_blocks, int64_t window, double softcap) {
+  TORCH_CHECK(n_kv > 0 && n_q % n_kv == 0);
+  (void)max_blocks;  // the plan reads the query side only
+  return {attn_plan::hd64_takes((int)n_q, (int)n_kv, (int)hd, window, softcap),
+          attn_plan::hd64_waves(Tq, (int)B, (int)n_q, (int)n_kv)};
+}
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("prefill_plan", &prefill_plan,
@@ -198,6 +206,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("packed_prefill_plan", &packed_prefill_plan,
         "(taken by paged_attention_prefill, waves per workgroup) of the "
         "packed-row prefill kernel",
+        pybind11::arg("Tq"), pybind11::arg("B"), pybind11::arg("n_q"),
+        pybind11::arg("n_kv"), pybind11::arg("hd"),
+        pybind11::arg("max_blocks"), pybind11::arg("window") = 0,
+        pybind11::arg("softcap") = 0.0);
+  m.def("hd64_prefill_plan", &hd64_prefill_plan,
+        "(taken by paged_attention_prefill, waves per workgroup) of the "
+        "head_dim 64 prefill kernel",
         pybind11::arg("Tq"), pybind11::arg("B"), pybind11::arg("n_q"),
         pybind11::arg("n_kv"), pybind11::arg("hd"),
         pybind11::arg("max_blocks"), pybind11::arg("window") = 0,

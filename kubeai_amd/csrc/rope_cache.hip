@@ -128,8 +128,10 @@ void rope_and_cache(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   TORCH_CHECK(v_cache.scalar_type() == k_cache.scalar_type());
   const int T = q.size(0);
   const int n_q = q.size(1), n_kv = k.size(1), hd = q.size(2);
-  TORCH_CHECK(hd == 128 || hd == 256,
-              "rope_and_cache supports head_dim 128 or 256");
+  // the kernel takes hd at run time; a 64-element row is 128 B (bf16) or
+  // 64 B (e5m2), so the 16 B / 8 B vector accesses stay aligned
+  TORCH_CHECK(hd == 64 || hd == 128 || hd == 256,
+              "rope_and_cache supports head_dim 64, 128 or 256");
   TORCH_CHECK(k.size(0) == T && v.size(0) == T && k.size(2) == hd);
   TORCH_CHECK(v.size(1) == n_kv && v.size(2) == hd);
   TORCH_CHECK(cos_sin.size(1) == hd);

@@ -226,6 +226,59 @@ PRESETS: dict[str, ModelArchConfig] = {
         tie_word_embeddings=True,
         rope_theta=1000000.0,
     ),
+    # qwen2-tiny-g7 at the 0.5B models' head_dim 64 (7 heads x 64 = hidden
+    # 448): the hd-64 prefill and decode kernels at test size
+    "qwen2-tiny-hd64": ModelArchConfig(
+        vocab_size=2048,
+        hidden_size=448,
+        intermediate_size=512,
+        num_hidden_layers=2,
+        num_attention_heads=7,
+        num_key_value_heads=1,
+        head_dim=64,
+        max_position_embeddings=2048,
+        bos_token_id=1,
+        eos_token_id=2,
+        attention_bias=True,
+        tie_word_embeddings=True,
+        rope_theta=1000000.0,
+    ),
+    # Qwen2.5-0.5B-Instruct shape (Qwen2-0.5B shares it): 14 / 2 heads, G = 7,
+    # head_dim 64
+    "qwen2.5-0.5b": ModelArchConfig(
+        vocab_size=151936,
+        hidden_size=896,
+        intermediate_size=4864,
+        num_hidden_layers=24,
+        num_attention_heads=14,
+        num_key_value_heads=2,
+        head_dim=64,
+        max_position_embeddings=32768,
+        rms_norm_eps=1e-6,
+        rope_theta=1000000.0,
+        bos_token_id=151643,
+        eos_token_id=151645,
+        attention_bias=True,
+        tie_word_embeddings=True,
+    ),
+    # Llama-3.2-1B-Instruct shape: 32 / 8 heads, G = 4, head_dim 64
+    "llama-3.2-1b": ModelArchConfig(
+        vocab_size=128256,
+        hidden_size=2048,
+        intermediate_size=8192,
+        num_hidden_layers=16,
+        num_attention_heads=32,
+        num_key_value_heads=8,
+        head_dim=64,
+        max_position_embeddings=131072,
+        rope_theta=500000.0,
+        tie_word_embeddings=True,
+        bos_token_id=128000,
+        eos_token_id=128009,
+        rope_scaling={"rope_type": "llama3", "factor": 32.0,
+                      "low_freq_factor": 1.0, "high_freq_factor": 4.0,
+                      "original_max_position_embeddings": 8192},
+    ),
     "qwen2-7b": ModelArchConfig(
         vocab_size=152064,
         hidden_size=3584,

@@ -159,7 +159,9 @@ def rope_cache_attention_decode(
     block block_tables[b][(L-1) // 16] with L = seq_lens[b], or negative
     (graph pad row: nothing is cached, the row attends what the cache
     holds). q, k and v keep independent row strides."""
-    if q.is_cuda and decode_rope_fused():
+    # head_dim 64 has no rope-in-kernel form: its decode kernel
+    # (attention_decode_hd64.hip) takes rotated q, so the two launches run
+    if q.is_cuda and decode_rope_fused() and q.shape[-1] != 64:
         _require_ext()
         if out is None:
             out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
@@ -186,8 +188,8 @@ def rope_cache_attention_decode(
             o8, oscale = ref.quant_fp8(res.reshape(res.shape[0], -1))
             return res, o8, oscale
         return res
-    # GPU with the switch off: exactly the two launches, so q and k ARE
-    # rotated in place here, as rope_and_cache does
+    # GPU with the switch off, or head_dim 64: exactly the two launches, so q
+    # and k ARE rotated in place here, as rope_and_cache does
     qr, _ = rope_and_cache(
         q, k, v, positions, cos_sin, k_cache, v_cache, slot_mapping
     )
