@@ -82,6 +82,11 @@ void mxfp4_gemm(torch::Tensor y, torch::Tensor xq, torch::Tensor xs,
                 torch::Tensor qp, torch::Tensor sp, int64_t N, int64_t K,
                 int64_t n_tiles);
 std::tuple<int64_t, int64_t> mxfp4_plan(int64_t M, int64_t N);
+// the output-tiled kernel for M > 64 (mxfp4_gemm_tiled.hip)
+void mxfp4_gemm_tiled(torch::Tensor y, torch::Tensor xq, torch::Tensor xs,
+                      torch::Tensor qp, torch::Tensor sp, int64_t N, int64_t K,
+                      int64_t bm, int64_t bn);
+std::tuple<int64_t, int64_t> mxfp4_tiled_plan(int64_t M, int64_t N);
 void greedy_sample(torch::Tensor out, torch::Tensor logits);
 void gumbel_sample(torch::Tensor out, torch::Tensor logits,
                    torch::Tensor temperature, torch::Tensor seeds,
@@ -294,6 +299,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mxfp4_plan", &mxfp4_plan,
         "(16-row tiles, 16-column tiles per workgroup) mxfp4_gemm launches "
         "with", pybind11::arg("M"), pybind11::arg("N"));
+  m.def("mxfp4_gemm_tiled", &mxfp4_gemm_tiled,
+        "y = bf16((xq @ W^T) * xs) over a packed MXFP4 weight, output-tiled "
+        "on the scaled MFMA, any M >= 1; bm = bn = 0 takes "
+        "mxfp4_tiled_plan's tile form",
+        pybind11::arg("y"), pybind11::arg("xq"), pybind11::arg("xs"),
+        pybind11::arg("qp"), pybind11::arg("sp"), pybind11::arg("N"),
+        pybind11::arg("K"), pybind11::arg("bm") = 0, pybind11::arg("bn") = 0);
+  m.def("mxfp4_tiled_plan", &mxfp4_tiled_plan,
+        "(BM, BN): the output tile mxfp4_gemm_tiled launches with",
+        pybind11::arg("M"), pybind11::arg("N"));
   m.def("greedy_sample", &greedy_sample, "argmax sampling");
   m.def("gumbel_sample", &gumbel_sample, "temperature sampling (hash RNG)");
   m.def("greedy_sample_logprob", &greedy_sample_logprob,

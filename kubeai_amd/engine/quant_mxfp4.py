@@ -7,7 +7,9 @@ gfx950's scaled matrix instruction (csrc/mxfp4_gemm.hip): there is no
 dequantization step at all, and the activations are the (e4m3 rows, fp32 row
 scale) pairs that the fused norm, activation and attention-merge kernels
 already emit. Larger M dequantize into the shared bf16 workspace and run the
-library GEMM.
+library GEMM, unless KUBEAI_MXFP4_TILED_M raises ops.mxfp4_m_max(): steps of up
+to that many rows then stay on the scaled MFMA, in the output-tiled kernel
+(csrc/mxfp4_gemm_tiled.hip).
 
 The pinned semantics (OCP MX v1.0): an e2m1 code (sign, 2 exponent bits, 1
 mantissa bit) is one of +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, and
@@ -239,12 +241,12 @@ class Mxfp4Linear(nn.Module):
 
     def forward_quantized(self, xq: torch.Tensor, xs: torch.Tensor) -> torch.Tensor:
         """Pre-quantized input from a fused producer kernel: e4m3 [M, K] and
-        fp32 row scales, M <= ops.MXFP4_M_FUSED (the layer code sends no
+        fp32 row scales, M <= ops.mxfp4_m_max() (the layer code sends no
         more)."""
-        if xq.shape[0] > ops.MXFP4_M_FUSED:
+        if xq.shape[0] > ops.mxfp4_m_max():
             raise RuntimeError(
                 f"Mxfp4Linear.forward_quantized takes at most "
-                f"{ops.MXFP4_M_FUSED} rows, got {xq.shape[0]}"
+                f"{ops.mxfp4_m_max()} rows, got {xq.shape[0]}"
             )
         y = ops.mxfp4_linear(xq, xs, self.mxfp4)
         return y + self.bias if self.bias is not None else y
@@ -256,7 +258,7 @@ class Mxfp4Linear(nn.Module):
             )
         if not x.is_cuda:
             y = torch.nn.functional.linear(x, self.mxfp4.dequant())
-        elif 1 <= x.shape[0] <= ops.MXFP4_M_FUSED:
+        elif 1 <= x.shape[0] <= ops.mxfp4_m_max():
             y = ops.mxfp4_linear(*ops.quant_fp8(x.contiguous()), self.mxfp4)
         else:
             dense = ops.mxfp4_dequant(
@@ -275,7 +277,7 @@ _TARGETS = ("qkv_proj", "o_proj", "gate_up_proj", "down_proj")
 def convert_to_mxfp4(model: nn.Module) -> int:
     """Swap the target nn.Linear modules of a dense model for Mxfp4Linear,
     round-to-nearest; returns the count. lm_head stays bf16. Each decoder
-    layer is marked so that steps of at most ops.MXFP4_M_FUSED rows take its
+    layer is marked so that steps of at most ops.mxfp4_m_max() rows take its
     fused-fp8 branch (llama.DecoderLayer.fp8_fused): norms, activation and
     attention merge emit e4m3 rows and the linears consume them as they are."""
     n = 0

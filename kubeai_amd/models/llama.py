@@ -416,14 +416,14 @@ class DecoderLayer(nn.Module):
     def fp8_fused(self, fb, on_gpu: bool) -> bool:
         """Whether forward takes the fused-fp8 branch for this batch. An
         MXFP4 layer (_mxfp4_fused, set by convert_to_mxfp4) takes it for the
-        steps its scaled-MFMA kernel serves: at most ops.MXFP4_M_FUSED rows."""
+        steps its scaled-MFMA kernels serve: at most ops.mxfp4_m_max() rows."""
         return (
             not self.post_norms
             and (
                 getattr(self, "_fp8_fused", False)
                 or (
                     getattr(self, "_mxfp4_fused", False)
-                    and fb.input_ids.shape[0] <= ops.MXFP4_M_FUSED
+                    and fb.input_ids.shape[0] <= ops.mxfp4_m_max()
                 )
             )
             and on_gpu

@@ -394,6 +394,15 @@ def int4_linear(x, w):
 MXFP4_M_FUSED = 64
 
 
+def mxfp4_m_max() -> int:
+    """Largest M the scaled-MFMA kernels serve: MXFP4_M_FUSED, or
+    KUBEAI_MXFP4_TILED_M where that is larger. Steps of MXFP4_M_FUSED < M <=
+    mxfp4_m_max() run the output-tiled kernel (mxfp4_gemm_tiled) and keep the
+    decoder layers in their fused-fp8 branch. Read at call time; unset, no
+    route moves. See docs/kernels.md for the recommended value."""
+    return max(MXFP4_M_FUSED, int(os.environ.get("KUBEAI_MXFP4_TILED_M", "0")))
+
+
 def mxfp4_dequant(w, out=None):
     """Packed MXFP4 weight -> bf16 [N, K], bit-identical to w.dequant()."""
     if not w.qp.is_cuda:
@@ -412,14 +421,26 @@ def mxfp4_dequant(w, out=None):
 def mxfp4_linear(xq, xs, w):
     """y[m, n] = bf16(acc[m, n] * xs[m]), acc the fp32 sum over k of the exact
     products xq[m, k] * w.dequant()[n, k]: bf16 [M, N]. xq is e4m3 [M, K] with
-    16-byte aligned rows, xs its fp32 row scales [M] or [M, 1], 1 <= M <= 64.
-    One launch on GPU, and a row's bytes do not depend on the rows around it."""
+    16-byte aligned rows, xs its fp32 row scales [M] or [M, 1], 1 <= M <=
+    mxfp4_m_max(). One launch on GPU, and a row's bytes do not depend on the
+    rows around it: up to MXFP4_M_FUSED rows mxfp4_gemm (eight K-split
+    partials summed in wave order), above it mxfp4_gemm_tiled (one accumulator
+    per output over all of K). The two kernels agree with the exact product
+    wherever fp32 summation is exact, not bit for bit elsewhere."""
     if not xq.is_cuda:
         acc = xq.float() @ w.dequant().float().t()
         return (acc * xs.reshape(-1, 1).float()).to(torch.bfloat16)
     _require_ext()
-    y = torch.empty((xq.shape[0], w.N), dtype=torch.bfloat16, device=xq.device)
-    _C.mxfp4_gemm(y, xq, xs, w.qp, w.sp, w.N, w.K)
+    M = xq.shape[0]
+    if M > mxfp4_m_max():
+        raise RuntimeError(
+            f"mxfp4_linear takes at most {mxfp4_m_max()} rows, got {M}"
+        )
+    y = torch.empty((M, w.N), dtype=torch.bfloat16, device=xq.device)
+    if M <= MXFP4_M_FUSED:
+        _C.mxfp4_gemm(y, xq, xs, w.qp, w.sp, w.N, w.K)
+    else:
+        _C.mxfp4_gemm_tiled(y, xq, xs, w.qp, w.sp, w.N, w.K)
     return y
 
 
